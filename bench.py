@@ -1,6 +1,12 @@
 """Benchmark: RK45 ray-steps/s of the MI355X ray integrator (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--days D] [--bg zonal|nonzonal]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; ``--full``
+adds everything else the line can carry (``roofline``, ``cpu_baseline``, the
+parity checks against the oracle).  ``--dump-outputs DIR`` writes what the last
+timed step returned to its caller as ``DIR/<name>.npy``.
 
 One "step" = one pass of the hot path over ONE ray set: the whole C3 workload
 (2-degree global seed grid x k = 1..10 x periods {inf, 50, 30, 20, 10} d =
@@ -21,7 +27,7 @@ rank 0 over RCCL.  value = the set's accepted ray-steps / the slowest rank's
 wall time.  ``--scaling weak`` (every rank its own C3 set) is a diagnostic:
 its aggregate is reported under ``weak_scaling``, never as ``value``.
 
-Rank 0 prints ONE JSON line.  ``roofline`` prices the ray-loop kernel at the
+Rank 0 prints ONE JSON line.  With ``--full``, ``roofline`` prices the ray-loop kernel at the
 bound it actually hits -- VALU instruction issue at one wave per SIMD (PMC
 SQ_INSTS_VALU x 4 cycles against 1024 SIMDs x the in-kernel clock) -- with the
 real HBM traffic (PMC) and the algorithmic 2112 B per ray-step of SURVEY.md
@@ -149,6 +155,65 @@ def endpoint_sha(ends):
     e = ends.detach().cpu().numpy().astype(np.float64, copy=True)
     e[np.isnan(e)] = np.nan
     return hashlib.sha256(np.ascontiguousarray(e).tobytes()).hexdigest()[:16]
+
+
+DUMP_BUDGET = 62_000_000       # bytes of one --dump-outputs directory, all files together
+
+
+def finite_with_mask(a):
+    """``(values, mask)``: ``a [n, ncol]`` with every file value finite.  The
+    path returns NaN for a masked ray (wr.py:838-850: its row from the mask
+    on); in the file such a value is 0 and ``mask [n]`` (float32; None if
+    ``a`` holds no NaN) has bit c set where column c was NaN.  An infinity
+    becomes the format's largest finite value with its sign."""
+    nan = np.isnan(a)
+    mask = None
+    if nan.any():
+        assert a.ndim == 2 and a.shape[1] <= 24          # (a float32 holds 24 bits exactly)
+        mask = (nan * (1 << np.arange(a.shape[1]))).sum(axis=1).astype(np.float32)
+    return np.nan_to_num(a, nan=0.0), mask
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET, seed=0):
+    """``--dump-outputs``: per-ray arrays (``{name: [nray, ...]}``, row i of
+    every array belongs to the same ray) written as ``path/<name>.npy``,
+    float32 kept, anything else as float64, every value finite: an array
+    with NaNs is written with zeros in their place and its per-row column
+    bitmask beside it as ``<name>_nan.npy`` (``finite_with_mask``).  Over
+    ``budget`` bytes in all, the same seeded sample of the rows (ascending)
+    of every array is written instead, so two runs with the same arguments
+    write the same rays.  Returns the number of rows written."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    for k in list(arrays):
+        arrays[k], mask = finite_with_mask(arrays[k])
+        if mask is not None:
+            arrays[k + "_nan"] = mask
+    nray = len(next(iter(arrays.values())))
+    assert all(len(a) == nray for a in arrays.values())
+    per_ray = sum(a.itemsize * int(np.prod(a.shape[1:])) for a in arrays.values())
+    keep = max(1, budget // max(per_ray, 1))
+    if nray > keep:
+        pick = np.sort(np.random.default_rng(seed).choice(nray, size=keep, replace=False))
+        arrays = {k: a[pick] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return min(nray, keep)
+
+
+def dump_endpoints(path, endpoints, counts, rays):
+    """What ``run_sharded`` handed rank 0 in the last timed step, for the rays
+    ``rays`` (slot indices; the rays with an initial root): their last rows
+    ``endpoints.npy [n, 8]`` (lon lat k l amp ug vg accepted) in float64, their
+    accepted / rejected step counters ``counts.npy [n, 2]`` in float32 (exact
+    below 2^24) and the slots themselves, ``ray_index.npy [n]``.  A ray masked
+    before the end has NaNs in its last row: zeros in ``endpoints.npy``, the
+    columns flagged in ``endpoints_nan.npy [n]`` (``dump_outputs``)."""
+    rays = rays.to(endpoints.device)
+    return dump_outputs(path, {"endpoints": endpoints[rays].cpu().numpy(),
+                               "counts": counts[rays].cpu().numpy().astype(np.float32),
+                               "ray_index": rays.cpu().numpy().astype(np.float64)})
 
 
 def find_profile(name, path, workload, schedule):
@@ -360,11 +425,18 @@ def main():
                          "(tests the launcher without a GPU)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the roofline, the CPU baselines (unless --no-cpu) and the "
+                         "parity checks against the oracle (C5: the 10-day fixture sample)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0: the last row "
+                         "and step counters of the rays with an initial root) as DIR/<name>.npy, every "
+                         "value finite (NaNs written as 0 and flagged in DIR/<name>_nan.npy)")
     ap.add_argument("--days", type=float, default=90.0, help="integration horizon per step")
     ap.add_argument("--chunk", type=int, default=0, help="output rows per kernel launch")
     ap.add_argument("--cpu-rays", type=int, default=16384)
     ap.add_argument("--cpu-days", type=float, default=12.0)   # ~10 s of 1-core oracle work
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-procs", type=int, default=16,
                     help="processes of the multi-core CPU baseline (1: skip it)")
     ap.add_argument("--periods", type=int, default=5, help="C3 periods in the batch (1-5)")
@@ -408,6 +480,8 @@ def main():
     ap.add_argument("--replicate", type=int, default=1,
                     help="diagnostic: repeat the ray batch k times (more rays per lane)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.order is None:
         args.order = "cell" if args.config == "C5" else "priority"
     how, world = resolve_world(args.gpus)
@@ -460,9 +534,11 @@ def main():
     # weak scaling: rank r traces the C3 seed grid shifted by r x dlon / N
     # degrees of longitude (N GPUs: an N-times denser grid; rank 0 = C3)
     offset = rank * S.config("C3").dlon / world if weak else 0.0
+    # the host's initial rows: --full compares the GPU's with them and samples
+    # the CPU baseline's rays from them
     t_init = time.perf_counter()
-    y0 = c3_initial_state(bs, offset, periods=periods) if (rank == 0 or args.replicate > 1) else None
-    t_init = time.perf_counter() - t_init
+    y0 = c3_initial_state(bs, offset, periods=periods) if ((rank == 0 and args.full) or args.replicate > 1) else None
+    t_init = time.perf_counter() - t_init if y0 is not None else None
     if args.replicate > 1:
         y0 = np.concatenate([y0] * args.replicate, axis=1)
     # the basic state every rank integrates through is rank 0's (bs.py:202-262
@@ -631,14 +707,21 @@ def main():
                                   "threshold": eng.SPLIT_RHO, "rows": eng.SPLIT_ROWS},
             "library": os.path.basename(os.environ.get("RWRT_LIB", "librwrt.so")),
             "library_sha256": library_sha(),
-            "roofline": roofline(per_launch_steps, avg_launch_s, workload, schedule, BYTES_PER_STEP, args,
-                                 steps_per_s_gpu=value / world),
         }
+        if args.dump_outputs:
+            if weak:   # (every rank its own set: rank 0's own last rows, as gathered)
+                dump_outputs(args.dump_outputs, {"endpoints": ends0.cpu().numpy(),
+                                                 "ray_index": live_idx.cpu().numpy().astype(np.float64)})
+            else:
+                dump_endpoints(args.dump_outputs, r.endpoints, r.counts, live_idx)
+        if args.full:
+            result["roofline"] = roofline(per_launch_steps, avg_launch_s, workload, schedule, BYTES_PER_STEP, args,
+                                          steps_per_s_gpu=value / world)
         if weak and "all" in gathered:
             result["gathered_endpoints"] = {
                 "rows_per_rank": n_live_max, "bytes": world * n_live_max * 64,
                 "alive_at_end": int(sum(int((~torch.isnan(b[:, 0])).sum().item()) for b in gathered["all"]))}
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             pick, hist, csteps, cdt, cnt, crej, ccols = cpu_baseline(bg, y0, args.cpu_rays, args.cpu_days)
             # the reference's own loop shape, timed on the first half of the
             # same sample (~2x the RHS work per step)
@@ -877,8 +960,13 @@ def main_c5(args, dist, group, rank, world, dev, share=1):
         schedule = [args.probe] + [b - a for a, b in r.res.bounds]
         del out
         torch.cuda.empty_cache()
-        parity = c5_parity_sample(eng, torch.cat([x.reshape(7, -1) for x in rows], dim=1), args.fields, dev) \
-            if args.days >= 10 else {"skipped": "needs --days >= 10 (the fixture's horizon)"}
+        if args.dump_outputs and r.endpoints is not None:
+            dump_endpoints(args.dump_outputs, r.endpoints, r.counts, torch.nonzero(~torch.isnan(y0.sum(0))).squeeze(1))
+        if not args.full:
+            parity = {"skipped": "needs --full"}
+        else:
+            parity = c5_parity_sample(eng, torch.cat([x.reshape(7, -1) for x in rows], dim=1), args.fields, dev) \
+                if args.days >= 10 else {"skipped": "needs --days >= 10 (the fixture's horizon)"}
         c5_line = {
             "metric": METRIC, "value": tot_steps / max_el, "unit": "ray-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * max_el / args.steps,
@@ -908,9 +996,10 @@ def main_c5(args, dist, group, rank, world, dev, share=1):
                                           "the timed steps (bs.py:202-262 reads the file on one process)"),
             "queue_order": args.order,
             "library_sha256": library_sha(),
-            "init": "GPU rwrt_ray_initial inside every timed step",
-            "roofline": roofline(per_launch_steps, avg_launch_s, workload, schedule, bps, args, bound="hbm",
-                                 steps_per_s_gpu=tot_steps / max_el / world)}
+            "init": "GPU rwrt_ray_initial inside every timed step"}
+        if args.full:
+            c5_line["roofline"] = roofline(per_launch_steps, avg_launch_s, workload, schedule, bps, args, bound="hbm",
+                                           steps_per_s_gpu=tot_steps / max_el / world)
         if weak and world > 1:
             c5_line["weak_scaling"] = {"value": c5_line["value"], "unit": "ray-steps/s",
                                        "note": f"{world} x the C5 set: a diagnostic, not BASELINE configs[4]"}

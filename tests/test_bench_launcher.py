@@ -93,6 +93,61 @@ def test_roofline_hbm_bound_for_c5(tmp_path):
     assert v["bound"] == "valu_issue" and v["hbm"]["frac"] == r["frac"]
 
 
+def _load_dump(d, names):
+    """A dump read back as its caller saw it: NaN again where <name>_nan.npy flags the column."""
+    import numpy as np
+    out = {}
+    for k in names:
+        a = np.load(d / f"{k}.npy")
+        assert np.isfinite(a).all(), k                  # every value in a file is finite
+        if (d / f"{k}_nan.npy").exists():
+            m = np.load(d / f"{k}_nan.npy")
+            assert m.dtype == np.float32 and m.shape == (len(a),) and np.isfinite(m).all()
+            nan = (m.astype(np.int64)[:, None] >> np.arange(a.shape[1])) & 1 == 1
+            assert np.all(a[nan] == 0)
+            a = np.where(nan, np.nan, a)
+        out[k] = a
+    return out
+
+
+def test_dump_outputs_whole_then_sampled(tmp_path):
+    """--dump-outputs: every array whole under the byte budget; over it, the
+    same seeded, ascending sample of the rows of every array, the same from
+    call to call; float32 stays, anything else is written as float64; every
+    value written is finite, NaNs flagged per row and column beside the array
+    and infinities at the format's largest value."""
+    import numpy as np
+    import bench
+    n = 1000
+    ends = np.arange(n * 8, dtype=np.float64).reshape(n, 8)
+    ends[::7, 0] = np.nan
+    ends[::11, :7] = np.nan
+    ends[5, 7] = np.nan
+    arrays = {"endpoints": ends, "counts": np.arange(n * 2, dtype=np.int32).reshape(n, 2).astype(np.float32),
+              "ray_index": np.arange(n)}
+    per_ray = 64 + 8 + 8 + 4                            # (+ the endpoints' NaN mask)
+    assert bench.dump_outputs(str(tmp_path / "a"), arrays, budget=n * per_ray) == n
+    assert sorted(os.listdir(tmp_path / "a")) == ["counts.npy", "endpoints.npy", "endpoints_nan.npy", "ray_index.npy"]
+    got = _load_dump(tmp_path / "a", arrays)
+    assert got["endpoints"].dtype == np.float64 and got["counts"].dtype == np.float32
+    assert got["ray_index"].dtype == np.float64
+    for k in arrays:
+        assert np.array_equal(got[k], arrays[k], equal_nan=True)
+    keep = 300
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), arrays, budget=keep * per_ray + per_ray - 1) == keep
+    b, c = (_load_dump(tmp_path / d, arrays) for d in ("b", "c"))
+    idx = b["ray_index"].astype(np.int64)
+    assert len(idx) == keep and np.all(np.diff(idx) > 0)
+    for k in arrays:
+        assert np.array_equal(b[k], arrays[k][idx], equal_nan=True)     # one sample for every array
+        assert np.array_equal(b[k], c[k], equal_nan=True)               # and the same again
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= keep * per_ray + 4 * 128
+    assert bench.DUMP_BUDGET <= 64_000_000 - 4 * 128
+    v, m = bench.finite_with_mask(np.array([[np.inf, -np.inf, 1.0]]))
+    assert m is None and np.array_equal(v, [[np.finfo(np.float64).max, -np.finfo(np.float64).max, 1.0]])
+
+
 def test_schedule_defaults():
     """The bench's schedule defaults by what one GPU holds (a whole C3 set,
     zonal or not, a split one, C5); explicit values are kept."""

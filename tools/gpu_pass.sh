@@ -5,8 +5,8 @@
 # steps:
 #   suite[:<pytest -k expr>]     the -m gpu suite (or the selected tests)
 #   smoke                        __graft_entry__.smoke()
-#   bench[:<bench.py args>]      one bench line (--no-cpu unless args say otherwise)
-#   driver                       the driver's command: bench.py --gpus 1 (with the CPU baseline)
+#   bench[:<bench.py args>]      one bench line (--full --no-cpu, then the args)
+#   driver                       bench.py --gpus 1 --full (with the CPU baseline)
 #   ab:<lib>,<lib>..:<reps>[:<bench args>]   interleaved A/B bench lines of library builds
 #   prof:<tag>[:<bench args>]    same-build profile (tools/profile_round.sh <tag> <args>)
 #   py:<script and args>         python3 <script and args>
@@ -34,11 +34,11 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 1; }
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 900 python -u bench.py --no-cpu $rest > $O/bench_$n.log 2>&1 || { tail -20 $O/bench_$n.log; exit 1; }
+      timeout -k 10 900 python -u bench.py --full --no-cpu $rest > $O/bench_$n.log 2>&1 || { tail -20 $O/bench_$n.log; exit 1; }
       grep '^{' $O/bench_$n.log > $O/bench_$n.json
       echo "bench $rest: $(line < $O/bench_$n.json)" ;;
     driver)
-      timeout -k 10 900 python -u bench.py --gpus 1 $rest > $O/bench_driver_$n.log 2>&1 || { tail -20 $O/bench_driver_$n.log; exit 1; }
+      timeout -k 10 900 python -u bench.py --gpus 1 --full $rest > $O/bench_driver_$n.log 2>&1 || { tail -20 $O/bench_driver_$n.log; exit 1; }
       grep '^{' $O/bench_driver_$n.log > $O/bench_driver_$n.json
       echo "driver: $(line < $O/bench_driver_$n.json)" ;;
     ab)
@@ -47,7 +47,7 @@ for step in "$@"; do
       for r in $(seq 1 $reps); do
         for lib in ${libs//,/ }; do
           f=$O/ab_${n}_$(basename $lib .so)_$r
-          timeout -k 10 600 python -u bench.py --no-cpu --lib $lib $args > $f.log 2>&1 || { tail -20 $f.log; exit 1; }
+          timeout -k 10 600 python -u bench.py --full --no-cpu --lib $lib $args > $f.log 2>&1 || { tail -20 $f.log; exit 1; }
           grep '^{' $f.log > $f.json
           echo "ab $r $(basename $lib): $(line < $f.json)"
         done
@@ -56,7 +56,7 @@ for step in "$@"; do
       tag=${rest%%:*}; args=${rest#*:}; [ "$args" = "$rest" ] && args=""
       bash tools/profile_round.sh $tag $args || exit 1
       S=gpurun_out/prof_$tag/summary
-      timeout -k 10 900 python -u bench.py --no-cpu --valu-profile $S/valu.json --traffic $S/traffic.json $args \
+      timeout -k 10 900 python -u bench.py --full --no-cpu --valu-profile $S/valu.json --traffic $S/traffic.json $args \
         > $O/bench_prof_$tag.log 2>&1 || { tail -20 $O/bench_prof_$tag.log; exit 1; }
       grep '^{' $O/bench_prof_$tag.log > $S/bench_line.json
       echo "prof $tag: $(line < $S/bench_line.json)" ;;

@@ -7,7 +7,7 @@ set -e
 r=$1; shift
 export TMPDIR=/tmp
 out=gpurun_out/prof_$r; sum=$out/summary; mkdir -p $out $sum
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu $*"
+B="python3 bench.py --steps 2 --warmup 1 --full --no-cpu $*"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- $B > $out/trace.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/fetch -o run --output-format csv -- $B > $out/fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $out/write -o run --output-format csv -- $B > $out/write.log 2>&1
