@@ -33,8 +33,9 @@
 extern "C" {
 #endif
 
-#define RWRT_ABI_VERSION 4  /* 3: constant row tails (rwrt_rk45_run_tails, rwrt_expand_tails);
-                               4: row blocks for the live rays only (rwrt_rk45_run_slots) */
+#define RWRT_ABI_VERSION 5  /* 3: constant row tails (rwrt_rk45_run_tails, rwrt_expand_tails);
+                               4: row blocks for the live rays only (rwrt_rk45_run_slots);
+                               5: ray-density maps binned on the device (rwrt_ray_density) */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -278,6 +279,51 @@ rwrt_status rwrt_rk45_run_slots(rwrt_ctx* ctx, const rwrt_grid* g, const double*
 rwrt_status rwrt_expand_slots(int64_t nray, int32_t it_begin, int32_t it_end, const int32_t* d_row_slot,
                               const int32_t* d_tail_from, const double* d_tail_row, const double* d_rows,
                               double* d_out, void* stream);
+
+/* ABI 5: ray-density maps.  The output rows of a ray-loop call are binned
+ * where they lie instead of being shipped to the host: how many ray points
+ * fall into each box of a regular lon-lat map, optionally with the sum of one
+ * row column (the amplitude), in nchan maps selected per ray.  The definition
+ * is density.reference_bins (NumPy); csrc/density_bins.h restates it and the
+ * counts equal NumPy's exactly.  For a row point (lon, lat, w) of a ray with
+ * channel c:
+ *   lam = (lon % 2 pi) % 2 pi          (Python float %, as every lookup of the
+ *                                       ray loops wraps its longitude)
+ *   ix  = min(floor(lam * inv_dlon), nx - 1)
+ *   iy  = floor((lat - lat0) * inv_dlat)
+ * binned iff lon and lat are finite, 0 <= iy < ny, 0 <= c < nchan and, when
+ * wcol >= 0, w is finite: count[c][iy][ix] += 1 and wsum[c][iy][ix] += w.
+ * inv_dlon and inv_dlat are computed once by the caller (fp64) and never
+ * recomputed on the device. */
+typedef struct {
+  int32_t nx, ny, nchan, wcol;   /* wcol: -1 counts only, 2..6 also sum that row column */
+  double inv_dlon;               /* nx / (2 pi)          */
+  double lat0, inv_dlat;         /* rad; ny / (lat1-lat0) */
+} rwrt_density_map;              /* 40 bytes */
+
+/* Bins rows it_begin <= i < it_end of nray rays and ACCUMULATES into
+ * d_count[nchan][ny][nx] (int64) and, with wcol >= 0, d_wsum (fp64): the
+ * caller zeroes them once, so time chunks and shards add up.  Row layouts are
+ * those of the run entry points:
+ *  d_row_slot == NULL: dense rows d_rows[nray][rows][8];
+ *  otherwise row blocks d_rows[nslot][rows][8] with ray j in block
+ *    d_row_slot[j], -1: the ray has no block and all its rows are its tail
+ *    (tails are required with slots);
+ *  d_tail_from / d_tail_row non-NULL: rows i >= d_tail_from[j] (any value in
+ *    [it_begin, it_end]) are d_tail_row[j][8] and are not read from d_rows; a
+ *    finite tail adds its row count to one bin at once (the weight as
+ *    w * rows).
+ * d_chan[nray] (int32) is each ray's map, NULL: map 0 for every ray; a ray
+ * with a channel outside [0, nchan) is skipped.  Equal-bin runs of a ray's
+ * consecutive rows are combined before the atomic.  Counts are exact; the
+ * weighted sums depend on the arrival order in their last bits.  Asynchronous
+ * and ordered on `stream`; needs no rwrt_ctx.  nray == 0 is a no-op. */
+rwrt_status rwrt_ray_density(const rwrt_density_map* m, int64_t nray,
+                             int32_t it_begin, int32_t it_end,
+                             const double* d_rows, const int32_t* d_row_slot,
+                             const int32_t* d_tail_from, const double* d_tail_row,
+                             const int32_t* d_chan, int64_t* d_count, double* d_wsum,
+                             void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

@@ -20,7 +20,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_mercator_point", "rwrt_rhs", "rwrt_dp54_attempt",
                "rwrt_ray_initial", "rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails",
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
-               "rwrt_rk4_run",
+               "rwrt_rk4_run", "rwrt_ray_density",
                "rwrt_bs_ready", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
                "rwrt_rk45_run_tv_slots", "rwrt_rhs_tv",
                "rwrt_kat_rk45", "rwrt_selftest_math", "rwrt_host_fill_rows")
@@ -54,6 +54,13 @@ class Background(ctypes.Structure):
                 ("t0", ctypes.c_double), ("dt", ctypes.c_double)]
 
 
+class DensityMap(ctypes.Structure):
+    """``rwrt_density_map`` (ABI 5): the map a ``rwrt_ray_density`` call bins into."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nchan", ctypes.c_int32),
+                ("wcol", ctypes.c_int32), ("inv_dlon", ctypes.c_double),
+                ("lat0", ctypes.c_double), ("inv_dlat", ctypes.c_double)]
+
+
 _lib = None
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -73,6 +80,7 @@ def load():
     lib.rwrt_version.restype = ctypes.c_char_p
     lib.rwrt_last_error.restype = ctypes.c_char_p
     G, Pr, B = ctypes.POINTER(Grid), ctypes.POINTER(Params), ctypes.POINTER(Background)
+    M = ctypes.POINTER(DensityMap)
     sig = {
         "rwrt_pack_fields": [G, _P, _P, _P],
         "rwrt_mercator_point": [G, _P, _I64, _P, _P, _P, _P],
@@ -89,6 +97,7 @@ def load():
                                 _P, _P],
         "rwrt_expand_slots": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P],
         "rwrt_rk4_run": [_P, G, _P, _I64, Pr, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+        "rwrt_ray_density": [M, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_bs_ready": [_I32, _I32, _P, _P, _P, _D, _D, _P, _P, _I32, _P],
         "rwrt_rk45_init_tv": [G, B, _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
         "rwrt_rk45_run_tv": [_P, G, B, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],

@@ -1,0 +1,152 @@
+// density.hip -- rwrt_ray_density (ABI 5): ray-density maps binned on the
+// device from the row blocks and constant tails a ray-loop call has left.
+//
+// A translation unit of its own, linked into librwrt.so next to rwrt.hip, so
+// that the ray loops' code object is not touched by it.
+//
+// One lane walks one ray's rows of the call in order.  Consecutive rows of a
+// ray mostly fall into the same or a neighbouring bin, so the lane keeps the
+// current bin's run (rows, weight sum) in registers and issues one atomic per
+// run, not per row; a constant tail is one more run (rows x weight).  The map
+// does not fit LDS (1440 x 720 x 8 B = 8 MB per channel), so runs go straight
+// to global atomics: 64-bit integer adds for the counts (C5: 4.03 M rays x
+// 1 080 rows in one bin exceed 2^32) and the hardware fp64 add for the sums.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "rwrt.h"
+#include "density_bins.h"
+
+namespace rwrt {
+
+// (defined in rwrt.hip: the calling thread's last error, rwrt_last_error)
+rwrt_status fail(rwrt_status s, const char* fmt, const char* detail);
+rwrt_status check_launch(const char* what);
+
+namespace {
+
+struct DensityRun {
+  int32_t bin = -1;
+  unsigned long long n = 0;
+  double w = 0.0;
+};
+
+__device__ __forceinline__ void density_flush(const DensityRun& r, bool weighted,
+                                              unsigned long long* __restrict__ count,
+                                              double* __restrict__ wsum) {
+  if (r.bin < 0) return;
+  atomicAdd(count + r.bin, r.n);
+  if (weighted) unsafeAtomicAdd(wsum + r.bin, r.w);   // (global_atomic_add_f64, no compare-exchange loop)
+}
+
+// one more point (or `rows` equal points) of the lane's ray
+__device__ __forceinline__ void density_point(DensityRun& r, const rwrt_density_map& m, double lon, double lat,
+                                              double w, int32_t c, unsigned long long rows,
+                                              unsigned long long* __restrict__ count,
+                                              double* __restrict__ wsum) {
+  const int32_t b = density_bin(density_wrap_2pi(lon), lat, w, c, m);
+  if (b != r.bin) {
+    density_flush(r, m.wcol >= 0, count, wsum);
+    r.bin = b;
+    r.n = 0;
+    r.w = 0.0;
+  }
+  if (b < 0) return;   // (w may be NaN here: never summed)
+  r.n += rows;
+  r.w = r.w + w * (double)rows;   // (rows = 1: w itself)
+}
+
+constexpr int kDensityBatch = 4;   // rows loaded ahead per lane
+
+__global__ void __launch_bounds__(256)
+ray_density_kernel(const rwrt_density_map m, int64_t nray, int32_t it_begin, int32_t it_end,
+                   const double* __restrict__ rows, const int32_t* __restrict__ row_slot,
+                   const int32_t* __restrict__ tail_from, const double* __restrict__ tail_row,
+                   const int32_t* __restrict__ chan, unsigned long long* __restrict__ count,
+                   double* __restrict__ wsum) {
+  const int32_t nrows = it_end - it_begin;
+  const int wc = (m.wcol >= 0) ? m.wcol : 0;   // (a column that exists: its value is unused without a weight)
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < nray; j += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t c = chan ? chan[j] : 0;
+    if (c < 0 || c >= m.nchan) continue;
+    // rows [it_begin, tf) are read from the ray's block, rows [tf, it_end) are its tail
+    int32_t tf = it_end;
+    if (tail_from) tf = min(max(tail_from[j], it_begin), it_end);
+    int64_t blk = j;
+    if (row_slot) {
+      blk = row_slot[j];
+      if (blk < 0) tf = it_begin;   // no block: every row is the tail
+    }
+    DensityRun run;
+    const int32_t nread = tf - it_begin;
+    if (nread > 0) {
+      const double* __restrict__ r = rows + blk * (int64_t)nrows * RWRT_NOUT;
+      int32_t i = 0;
+      for (; i + kDensityBatch <= nread; i += kDensityBatch) {
+        double2 p[kDensityBatch];
+        double w[kDensityBatch];
+#pragma unroll
+        for (int k = 0; k < kDensityBatch; ++k) {
+          p[k] = *reinterpret_cast<const double2*>(r + (int64_t)(i + k) * RWRT_NOUT);
+          w[k] = r[(int64_t)(i + k) * RWRT_NOUT + wc];
+        }
+#pragma unroll
+        for (int k = 0; k < kDensityBatch; ++k) density_point(run, m, p[k].x, p[k].y, w[k], c, 1, count, wsum);
+      }
+      for (; i < nread; ++i) {
+        const double2 p = *reinterpret_cast<const double2*>(r + (int64_t)i * RWRT_NOUT);
+        density_point(run, m, p.x, p.y, r[(int64_t)i * RWRT_NOUT + wc], c, 1, count, wsum);
+      }
+    }
+    if (tf < it_end) {
+      const double* __restrict__ t = tail_row + j * RWRT_NOUT;
+      const double2 p = *reinterpret_cast<const double2*>(t);
+      density_point(run, m, p.x, p.y, t[wc], c, (unsigned long long)(it_end - tf), count, wsum);
+    }
+    density_flush(run, m.wcol >= 0, count, wsum);
+  }
+}
+
+}  // namespace
+}  // namespace rwrt
+
+using namespace rwrt;
+
+extern "C" rwrt_status rwrt_ray_density(const rwrt_density_map* m, int64_t nray, int32_t it_begin, int32_t it_end,
+                                        const double* d_rows, const int32_t* d_row_slot,
+                                        const int32_t* d_tail_from, const double* d_tail_row,
+                                        const int32_t* d_chan, int64_t* d_count, double* d_wsum, void* stream) {
+  // (every check before the first HIP call)
+  if (!m) return fail(RWRT_ERR_ARG, "rwrt_ray_density: map is NULL%s", "");
+  if (m->nx <= 0 || m->ny <= 0 || m->nchan <= 0)
+    return fail(RWRT_ERR_ARG, "rwrt_ray_density: nx, ny and nchan must be positive%s", "");
+  if ((int64_t)m->nx * m->ny >= (1LL << 31) || (int64_t)m->nx * m->ny * m->nchan >= (1LL << 31))
+    return fail(RWRT_ERR_ARG, "rwrt_ray_density: nchan*ny*nx must be below 2^31%s", "");
+  if (!(m->wcol == -1 || (m->wcol >= 2 && m->wcol <= 6)))
+    return fail(RWRT_ERR_ARG, "rwrt_ray_density: wcol must be -1 or 2..6 (k l amp ug vg)%s", "");
+  if (!(m->inv_dlon > 0.0) || !std::isfinite(m->inv_dlon))
+    return fail(RWRT_ERR_ARG, "rwrt_ray_density: inv_dlon must be finite and positive%s", "");
+  if (!(m->inv_dlat > 0.0) || !std::isfinite(m->inv_dlat))
+    return fail(RWRT_ERR_ARG, "rwrt_ray_density: inv_dlat must be finite and positive%s", "");
+  if (!std::isfinite(m->lat0)) return fail(RWRT_ERR_ARG, "rwrt_ray_density: lat0 must be finite%s", "");
+  if (m->wcol >= 0 && !d_wsum) return fail(RWRT_ERR_ARG, "rwrt_ray_density: wcol >= 0 needs d_wsum%s", "");
+  if (it_end <= it_begin) return fail(RWRT_ERR_ARG, "rwrt_ray_density: need it_begin < it_end%s", "");
+  if (nray < 0 || nray > 0x7fffffffLL) return fail(RWRT_ERR_ARG, "rwrt_ray_density: nray out of range%s", "");
+  if (!d_tail_from != !d_tail_row)
+    return fail(RWRT_ERR_ARG, "rwrt_ray_density: tails need both d_tail_from and d_tail_row%s", "");
+  if (d_row_slot && !d_tail_from)
+    return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_row_slot needs tails (d_tail_from, d_tail_row)%s", "");
+  if (!d_count) return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_count is NULL%s", "");
+  if (nray == 0) return RWRT_OK;
+  if (!d_rows) return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_rows is NULL%s", "");
+  if (reinterpret_cast<uintptr_t>(d_rows) % 16 != 0 || reinterpret_cast<uintptr_t>(d_tail_row) % 16 != 0)
+    return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_rows and d_tail_row must be 16-byte aligned%s", "");
+  const unsigned blocks = (unsigned)((nray + 255) / 256);
+  hipLaunchKernelGGL(ray_density_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *m, nray, it_begin,
+                     it_end, d_rows, d_row_slot, d_tail_from, d_tail_row, d_chan,
+                     reinterpret_cast<unsigned long long*>(d_count), d_wsum);
+  return check_launch("ray_density_kernel");
+}

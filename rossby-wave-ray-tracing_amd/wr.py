@@ -152,8 +152,13 @@ class WR:
         """The fixed-step RK4 ray loop on the GPU (replaces wr.py:702-765)."""
         return self._core_ray_run_hip("rk4", group)
 
-    def _core_ray_run_hip(self, method, group=None):
+    def _core_ray_run_hip(self, method, group=None, sink=None):
         """Shared driver of the two GPU ray loops.
+
+        ``sink`` (``ray_density``): a device-side consumer of the rows (the
+        engine's ``sink`` protocol, with ``take(idx)`` for a rank's shard)
+        that replaces the delivery into the history arrays -- no row reaches
+        the host and the arrays keep only row 0.
 
         With a torch.distributed ``group`` of one process per GPU, the rays are
         sharded over the ranks (shard.py): rank 0's basic state is broadcast,
@@ -176,13 +181,14 @@ class WR:
             idx = shard.shard_indices(~np.isnan(y0.mean(axis=0)), rank, world)
         rows_shape = (3, self.nsource, self.nzwn)
         hist = (self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)
+        own_sink = sink is None   # (deliver into the history arrays)
 
-        if multi:
+        if multi and own_sink:
             # each rank's previous rows (row 0: the initial rows), as bit patterns
             row0 = np.stack([h[0].reshape(-1)[idx] for h in hist], axis=1)
             last = torch.as_tensor(np.ascontiguousarray(row0)).view(torch.int64).to(eng.device)
 
-        def sink(i0, i1, rows):
+        def gather_sink(i0, i1, rows):
             # rank 0 receives only the rays whose rows changed; every other
             # ray repeats its previous row (hostio.fill_rows)
             got = shard.gather_changed_rows(rows, torch.as_tensor(idx, device=rows.device), last, 0, group)
@@ -201,7 +207,11 @@ class WR:
         chunk = self.chunk_rows or _default_chunk(nray, self.nt)
         grp = group if multi else None
         out, hs = None, None
-        if not multi:
+        if not own_sink:
+            sink = sink.take(idx) if multi else sink
+        elif multi:
+            sink = gather_sink
+        else:
             # single GPU: chunks reach the host arrays while the next one is
             # computed (permute on the device, pinned D2H, threaded copies)
             from hostio import HistorySink
@@ -224,11 +234,57 @@ class WR:
                 # ray-rows shipped over PCIe vs delivered (frozen rays' rows are filled on the host)
                 self.last_delivery = {"shipped_ray_rows": hs.shipped, "delivered_ray_rows": hs.delivered,
                                       "host_fill_s": hs.t_fill, "host_wait_s": hs.t_wait}
-        if res.break_row is not None:
+        if res.break_row is not None and own_sink:
             for h in hist:
                 h[res.break_row:] = np.nan     # rows never stored (wr.py:853-855, 886-887)
         self.last_run = res
         return res
+
+    def ray_density(self, spec, mode="hip", inte_method="rk45", by=None, include_initial=True,
+                    group=None, root_method="numpy"):
+        """Initialise and integrate all rays like ``ray_run``, but bin every
+        output row into a lon-lat map on the GPU (density.py) instead of
+        delivering the history: returns the ``density.DensityMap``; only row 0
+        of ``rlon .. rvg`` is filled.
+
+        ``spec``: a ``density.DensitySpec``.  ``by``: one map per zonal
+        wavenumber (``'zwn'``) or per root (``'root'``) -- sets the channel of
+        ray slot (root, source, zwn) and the number of maps; None: one map.
+        ``include_initial``: count row 0 (the sources) too.  ``mode='numpy'``
+        integrates on the GPU all the same, delivers the history and bins it
+        on the host with ``density.reference_bins`` (small runs; returns
+        ``(count, wsum)``).  With a process ``group`` every rank ends with the
+        sum over the ranks."""
+        import density as D
+        if by not in (None, "zwn", "root"):
+            raise ValueError("by must be None, 'zwn' or 'root'")
+        shape = (3, self.nsource, self.nzwn)
+        chan = None
+        if by is not None:
+            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
+            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
+            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
+        if mode == "numpy":
+            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
+            w = None if spec.wcol < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[spec.wcol - 2]
+            first = 0 if include_initial else 1
+            nray = 3 * self.nsource * self.nzwn
+            pts = [None if a is None else a[first:].reshape(-1, nray) for a in (self.rlon, self.rlat, w)]
+            return D.reference_bins(pts[0], pts[1], pts[2], None if chan is None else chan[None, :], spec)
+        key = mode + "_rk45" if inte_method == "rk45" else mode
+        if key not in SUPPORTED:
+            self.core_ray_run(key)     # raises before any work
+        self.ray_initial(mode=mode, root_method=root_method)
+        import shard
+        rank, world = shard.world_info(group) if group is not None else (0, 1)
+        dmap = D.DensityMap(spec, self.bs.engine().device)
+        if include_initial and rank == 0:
+            w0 = None if spec.wcol < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[spec.wcol - 2][0]
+            dmap.add_points(self.rlon[0], self.rlat[0], w0, chan)
+        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=D.DensitySink(dmap, chan))
+        if group is not None and shard.collective(world):
+            dmap.allreduce(group)
+        return dmap
 
     def core_ray_run(self, mode="hip_rk45", group=None):
         if mode not in SUPPORTED:

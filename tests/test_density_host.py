@@ -1,0 +1,265 @@
+"""Ray-density maps, host side (no GPU): the NumPy definition
+``density.reference_bins`` on hand-made corner points and on the reference's
+own C1 history, the shared index function csrc/density_bins.h in a
+stand-alone program under the sanitizers, and the argument checks of
+``rwrt_ray_density``."""
+import ctypes
+import math
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import _hip as H
+from conftest import golden
+from density import DensitySpec, bin_index, reference_bins
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TWO_PI = 2 * math.pi
+HALF_PI = math.pi / 2
+INF, NAN = math.inf, math.nan
+
+SPEC = DensitySpec(7, 5, nchan=2, weight="amp")     # 7 x 5 boxes of 51.4 x 36 degrees, two maps
+
+
+def corner_points():
+    """``(lon, lat, w, chan, expected)``: expected = (chan, iy, ix) written out
+    by hand, None for a point that is not binned."""
+    lat0, lat1 = -HALF_PI, HALF_PI
+    mid = 0.1          # (0.1 + pi/2) * 5/pi = 2.66 -> iy 2
+    pts = [
+        # longitudes (box width 2 pi / 7 = 0.8976 rad)
+        (0.0, mid, 1.0, 0, (0, 2, 0)),
+        (TWO_PI, mid, 1.0, 0, (0, 2, 0)),                       # 2 pi % 2 pi = 0
+        (-1e-20, mid, 1.0, 0, (0, 2, 0)),                       # % gives 2 pi, the second % gives 0
+        (math.nextafter(TWO_PI, 0.0), mid, 1.0, 0, (0, 2, 6)),  # the product floors to 7.0: clamped
+        (63.69, mid, 1.0, 0, (0, 2, 0)),                        # 63.69 - 10 * 2 pi = 0.858
+        (-5.0, mid, 1.0, 0, (0, 2, 1)),                         # 2 pi - 5 = 1.283
+        (3.2, mid, 1.0, 0, (0, 2, 3)),                          # 3.2 / 0.8976 = 3.57
+        # latitudes (box height pi / 5 = 0.6283 rad), map 1, lon 1.0 -> ix 1
+        (1.0, lat0, 1.0, 1, (1, 0, 1)),
+        # the last double below lat1: lat - lat0 rounds (to even) to pi itself, times 5/pi is 5.0 -> outside,
+        # as NumPy has it; two ulps further down the difference is below pi and the point is in the top row
+        (1.0, math.nextafter(lat1, 0.0), 1.0, 1, None),
+        (1.0, lat1 - 1e-9, 1.0, 1, (1, 4, 1)),
+        (1.0, lat1, 1.0, 1, None),                              # the upper edge is excluded
+        (1.0, math.nextafter(lat0, -INF), 1.0, 1, None),
+        (1.0, -0.3, 1.0, 1, (1, 2, 1)),                         # (-0.3 + pi/2) * 5/pi = 2.02
+        (1.0, -0.32, 1.0, 1, (1, 1, 1)),                        # 1.99
+        # non-finite and huge values
+        (NAN, mid, 1.0, 0, None), (INF, mid, 1.0, 0, None), (-INF, mid, 1.0, 0, None),
+        (1.0, NAN, 1.0, 0, None), (1.0, INF, 1.0, 0, None), (1.0, -INF, 1.0, 0, None),
+        (1.0, 1e300, 1.0, 0, None), (1.0, -1e300, 1.0, 0, None),
+        (1.0, mid, NAN, 0, None), (1.0, mid, INF, 0, None), (1.0, mid, -INF, 0, None),
+        (1.0, mid, 1e300, 0, (0, 2, 1)), (2.0, mid, -1e300, 0, (0, 2, 2)),   # finite weights count
+        # channels outside [0, nchan)
+        (1.0, mid, 1.0, -1, None), (1.0, mid, 1.0, 2, None),
+    ]
+    # a huge finite longitude is binned where Python's % puts it
+    for big in (1e300, -1e300):
+        lam = (big % TWO_PI) % TWO_PI
+        pts.append((big, mid, 1.0, 1, (1, 2, min(math.floor(lam * SPEC.inv_dlon), 6))))
+    return pts
+
+
+def scalar_bin(lon, lat, w, c, spec):
+    """The definition of the issue, point by point in Python floats."""
+    if not (math.isfinite(lon) and math.isfinite(lat)) or not 0 <= c < spec.nchan:
+        return None
+    if spec.wcol >= 0 and not math.isfinite(w):
+        return None
+    lam = (lon % TWO_PI) % TWO_PI
+    ix = min(math.floor(lam * spec.inv_dlon), spec.nx - 1)
+    fy = (lat - spec.lat0) * spec.inv_dlat
+    if not math.isfinite(fy) or not 0 <= math.floor(fy) < spec.ny:
+        return None
+    return (c, math.floor(fy), ix)
+
+
+def random_points(n, spec, seed=0):
+    rng = np.random.default_rng(seed)
+    lon = rng.uniform(-70.0, 70.0, n)
+    lat = rng.uniform(spec.lat0 - 0.2, spec.lat1 + 0.2, n)
+    w = rng.uniform(-2.0, 2.0, n)
+    chan = rng.integers(-1, spec.nchan + 1, n)
+    # some exactly on box edges, some non-finite
+    k = n // 10
+    lon[:k] = rng.integers(-20, 20, k) * (TWO_PI / spec.nx)
+    lat[k:2 * k] = spec.lat0 + rng.integers(-1, spec.ny + 2, k) * ((spec.lat1 - spec.lat0) / spec.ny)
+    lon[2 * k:2 * k + 20] = NAN
+    lat[2 * k + 20:2 * k + 40] = INF
+    w[2 * k + 40:2 * k + 60] = NAN
+    return lon, lat, w, chan
+
+
+def test_spec_factors():
+    s = DensitySpec(1440, 720)
+    assert (s.lat0, s.lat1) == (-HALF_PI, HALF_PI)
+    assert s.inv_dlon == 1440 / (2 * math.pi) and s.inv_dlat == 720 / (s.lat1 - s.lat0)
+    assert s.wcol == -1 and SPEC.wcol == 4
+    c = SPEC.c_struct()
+    assert (c.nx, c.ny, c.nchan, c.wcol, c.inv_dlon, c.lat0, c.inv_dlat) == \
+        (7, 5, 2, 4, SPEC.inv_dlon, SPEC.lat0, SPEC.inv_dlat)
+    with pytest.raises(ValueError):
+        DensitySpec(0, 5)
+    with pytest.raises(ValueError):
+        DensitySpec(7, 5, weight="nacc")
+
+
+def test_reference_bins_corner_points():
+    pts = corner_points()
+    lon, lat, w, chan = (np.array([p[k] for p in pts]) for k in range(4))
+    want = np.zeros(SPEC.shape, np.int64)
+    wsum_want = np.zeros(SPEC.shape)
+    for p in pts:
+        assert scalar_bin(*p[:4], SPEC) == p[4], p
+        if p[4] is not None:
+            want[p[4]] += 1
+            wsum_want[p[4]] += p[2]
+    count, wsum = reference_bins(lon, lat, w, chan.astype(np.int64), SPEC)
+    assert count.dtype == np.int64 and np.array_equal(count, want)
+    # written out: map 0, latitude row 2: 4 points at ix 0 (0, 2 pi, -1e-20, 63.69), the clamped one at 6
+    assert count[0, 2].tolist() == [4, 2, 1, 1, 0, 0, 1]
+    assert count[1, :, 1].tolist()[:2] == [1, 1] and count[1, 4, 1] == 1
+    assert count.sum() == sum(p[4] is not None for p in pts) == 15
+    assert np.array_equal(wsum, wsum_want)
+    # the clamp is needed at nx = 7 ...
+    assert math.floor(math.nextafter(TWO_PI, 0.0) * SPEC.inv_dlon) == 7
+    # ... and counts only: the same points with no weight bin the non-finite w too
+    s0 = DensitySpec(7, 5, nchan=2)
+    c0, w0 = reference_bins(lon, lat, None, chan.astype(np.int64), s0)
+    assert w0 is None and c0.sum() == 15 + 3
+
+
+def test_reference_bins_random_against_scalar_definition():
+    lon, lat, w, chan = random_points(4000, SPEC, seed=3)
+    idx = bin_index(lon, lat, w, chan, SPEC)
+    for i in range(len(lon)):
+        b = scalar_bin(float(lon[i]), float(lat[i]), float(w[i]), int(chan[i]), SPEC)
+        assert idx[i] == (-1 if b is None else (b[0] * SPEC.ny + b[1]) * SPEC.nx + b[2]), i
+
+
+@pytest.mark.parametrize("nx,ny", [(7, 5), (144, 72), (1440, 720)])
+def test_reference_bins_c1_history(nx, ny):
+    """The reference's own 90-day C1 history (rows 1..1080, 3 rays), full
+    latitude range: every one of the 3 240 points is binned; at 1440 x 720 the
+    fullest bin holds 1 080 (the contention case of the GPU tests)."""
+    g = golden("traj_C1.npz")
+    hist = g["hist"]                                  # (7, 1081, 3)
+    lon, lat = hist[0, 1:], hist[1, 1:]
+    assert np.nanmax(lon) > 63.0                      # stored longitudes are not wrapped
+    spec = DensitySpec(nx, ny)
+    count, wsum = reference_bins(lon, lat, None, None, spec)
+    assert wsum is None and count.shape == (1, ny, nx)
+    assert count.sum() == 3240
+    if (nx, ny) == (1440, 720):
+        assert count.max() == 1080
+    # per root through the channels: each root's 1 080 rows
+    by_root = reference_bins(lon, lat, None, np.arange(3)[None, :], DensitySpec(nx, ny, nchan=3))[0]
+    assert by_root.sum(axis=(1, 2)).tolist() == [1080, 1080, 1080]
+    assert np.array_equal(by_root.sum(0), count[0])
+
+
+def _build_host_program(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "density_bins_main")
+    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
+           "-fsanitize=undefined,address", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
+           "-fno-omit-frame-pointer",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
+           "-o", exe, os.path.join(ROOT, "tests", "host", "density_bins_main.cpp")]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "sanitize" in b.stderr and "density_bins" not in b.stderr:
+        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
+    assert b.returncode == 0, b.stderr[-3000:]
+    return exe
+
+
+@pytest.mark.parametrize("spec", [SPEC, DensitySpec(1440, 720), DensitySpec(144, 72, lat_range=(-30, 60), nchan=3,
+                                                                            weight="k")],
+                         ids=["7x5", "1440x720", "144x72-band"])
+def test_index_function_host_program_under_sanitizers(tmp_path, spec):
+    """csrc/density_bins.h (what the kernel calls) in a stand-alone program
+    built with ASan + UBSan + float-cast-overflow and run directly: the corner
+    points and 10^5 random ones give reference_bins' indices, and the wrapped
+    longitude equals Python's ``(lon % 2 pi) % 2 pi`` bit for bit."""
+    exe = _build_host_program(tmp_path)
+    pts = corner_points()
+    rl, rt, rw, rc = random_points(100000, spec, seed=11)
+    lon = np.concatenate([[p[0] for p in pts], rl])
+    lat = np.concatenate([[p[1] for p in pts], rt])
+    w = np.concatenate([[p[2] for p in pts], rw])
+    chan = np.concatenate([[p[3] for p in pts], rc]).astype(np.int64)
+    lines = [f"{spec.nx} {spec.ny} {spec.nchan} {spec.wcol} {spec.inv_dlon.hex()} {spec.lat0.hex()} "
+             f"{spec.inv_dlat.hex()}"]
+    lines += [f"{float(a).hex()} {float(b).hex()} {float(c).hex()} {int(d)}" for a, b, c, d in zip(lon, lat, w, chan)]
+    # (verify_asan_link_order=0: the environment may preload a library of its own)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    out = r.stdout.split()
+    got = np.array(out[0::2], dtype=np.int64)
+    lam = np.array([float.fromhex(x) if "nan" not in x else NAN for x in out[1::2]])
+    assert len(got) == len(lon)
+    want = bin_index(lon, lat, w, chan, spec)
+    bad = np.where(got != want)[0]
+    assert bad.size == 0, [(lon[i], lat[i], w[i], chan[i], got[i], want[i]) for i in bad[:5]]
+    with np.errstate(all="ignore"):
+        lam_want = np.remainder(np.remainder(lon, TWO_PI), TWO_PI)
+    assert np.array_equal(np.where(np.isnan(lam), NAN, lam).view(np.int64),
+                          np.where(np.isnan(lam_want), NAN, lam_want).view(np.int64))
+    for i in range(len(pts)):     # Python's own float %, point by point
+        if math.isfinite(pts[i][0]):
+            assert lam[i] == (pts[i][0] % TWO_PI) % TWO_PI
+
+
+# ----------------------------------------------------------- C entry point
+def _call(lib, m, nray=16, i0=1, i1=5, rows=64, slot=None, tfrom=None, trow=None, chan=None, count=64, wsum=None):
+    """rwrt_ray_density with fake (never dereferenced) device pointers."""
+    return lib.rwrt_ray_density(None if m is None else ctypes.byref(m), nray, i0, i1, rows, slot, tfrom, trow,
+                                chan, count, wsum, None)
+
+
+def test_density_argument_errors_without_a_gpu():
+    """Every check happens before any HIP call and names the argument."""
+    lib = H.load()
+    assert ctypes.sizeof(H.DensityMap) == 40
+    assert "abi 5" in H.version()
+    good = SPEC.c_struct()
+
+    def m(**kw):
+        c = SPEC.c_struct()
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+    cases = [
+        (dict(m=None), b"map"),
+        (dict(m=m(nx=0)), b"nx"), (dict(m=m(ny=-1)), b"ny"), (dict(m=m(nchan=0)), b"nchan"),
+        (dict(m=m(nx=65536, ny=32768, nchan=1)), b"2^31"), (dict(m=m(nx=1 << 20, ny=1 << 10, nchan=2)), b"2^31"),
+        (dict(m=m(wcol=0)), b"wcol"), (dict(m=m(wcol=1)), b"wcol"), (dict(m=m(wcol=7)), b"wcol"),
+        (dict(m=m(wcol=-2)), b"wcol"),
+        (dict(m=good, wsum=None), b"d_wsum"),
+        (dict(m=good, wsum=64, i0=5, i1=5), b"it_begin"), (dict(m=good, wsum=64, i0=6, i1=5), b"it_begin"),
+        (dict(m=good, wsum=64, slot=64), b"d_row_slot"),
+        (dict(m=good, wsum=64, tfrom=64), b"d_tail_row"), (dict(m=good, wsum=64, trow=64), b"d_tail_from"),
+        (dict(m=good, wsum=64, rows=None), b"d_rows"),
+        (dict(m=good, wsum=64, count=None), b"d_count"),
+        (dict(m=m(inv_dlon=0.0), wsum=64), b"inv_dlon"), (dict(m=m(inv_dlon=-1.0), wsum=64), b"inv_dlon"),
+        (dict(m=m(inv_dlon=INF), wsum=64), b"inv_dlon"), (dict(m=m(inv_dlon=NAN), wsum=64), b"inv_dlon"),
+        (dict(m=m(inv_dlat=0.0), wsum=64), b"inv_dlat"), (dict(m=m(inv_dlat=NAN), wsum=64), b"inv_dlat"),
+        (dict(m=m(inv_dlat=INF), wsum=64), b"inv_dlat"),
+        (dict(m=good, wsum=64, nray=-1), b"nray"),
+    ]
+    for kw, word in cases:
+        assert _call(lib, **kw) == H.RWRT_ERR_ARG, kw
+        assert word in lib.rwrt_last_error(), (kw, lib.rwrt_last_error())
+    # no rays: a no-op (no device is touched; there is none on the build host)
+    assert _call(lib, good, nray=0, rows=None, wsum=64) == H.RWRT_OK
+    assert _call(lib, m(wcol=-1), nray=0, rows=None, wsum=None) == H.RWRT_OK
