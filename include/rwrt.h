@@ -35,7 +35,9 @@ extern "C" {
 
 #define RWRT_ABI_VERSION 5  /* 3: constant row tails (rwrt_rk45_run_tails, rwrt_expand_tails);
                                4: row blocks for the live rays only (rwrt_rk45_run_slots);
-                               5: ray-density maps binned on the device (rwrt_ray_density) */
+                               5: ray-density maps binned on the device (rwrt_ray_density);
+                                  per-ray path summaries (rwrt_ray_summary) joined ABI 5 later as
+                                  an additive member: no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -324,6 +326,57 @@ rwrt_status rwrt_ray_density(const rwrt_density_map* m, int64_t nray,
                              const int32_t* d_tail_from, const double* d_tail_row,
                              const int32_t* d_chan, int64_t* d_count, double* d_wsum,
                              void* stream);
+
+/* ABI 5, additive: per-ray path summaries.  The same rows reduced per ray
+ * instead of per map box: how far the ray travelled, how often it was
+ * reflected, which latitudes it reached, where and when it stopped, and when
+ * and for how long it was inside up to RWRT_SUMMARY_MAXREG lon-lat boxes.  The
+ * definition is summary.reference_summary (NumPy); csrc/summary_rows.h restates
+ * it.  A row is valid iff lon and lat are finite; a path segment (the
+ * haversine angle of the reference's cal_dis) and a sign change of l are
+ * counted for row i iff rows i-1 and i are both valid.
+ *
+ * Accumulators are struct-of-arrays, one column per ray.
+ *  d_f64[RWRT_SUMMARY_NF64][nacc_cols], rows in this order:
+ *    lon_first lat_first   first valid row             (NaN: none yet)
+ *    lon_last lat_last l_last   last valid row         (NaN: none yet)
+ *    lat_min lat_max       over valid rows             (+inf / -inf)
+ *    amp_max               max |amp|, finite amp only  (-inf)
+ *    path                  radians, summed in row order (0)
+ *  d_i32[RWRT_SUMMARY_NI32 + 2 nreg][nacc_cols]:
+ *    n_valid (0)  last_row (-1)  n_turn (0)  prev_valid (0)
+ *    first_row[nreg]       first valid row inside box r (-1: never)
+ *    rows_inside[nreg]     valid rows inside box r      (0)
+ * The caller writes the initial values (in brackets) once; every call loads a
+ * ray's column, updates it with rows it_begin <= i < it_end and stores it, so
+ * a ray's rows may arrive in several calls.  The accumulators are a running
+ * state, not a sum: the calls for one ray must deliver CONSECUTIVE rows in
+ * order -- each call's it_begin equals the previous call's it_end (row 0, the
+ * initial row, is a call of its own with it_begin = 0) -- because prev_valid
+ * and lon_last, lat_last, l_last are the carried previous row.  Nothing
+ * checks that on the device.  Two rays must not share a column in one call. */
+#define RWRT_SUMMARY_MAXREG 8
+#define RWRT_SUMMARY_NF64 9
+#define RWRT_SUMMARY_NI32 4
+typedef struct {
+  int32_t nreg, reserved;                  /* 0 .. RWRT_SUMMARY_MAXREG boxes */
+  double box[RWRT_SUMMARY_MAXREG][4];      /* radians: lon_w lon_e lat_s lat_n; inside: lat_s <= lat < lat_n and,
+                                              lam = (lon % 2 pi) % 2 pi, lon_w <= lam < lon_e -- or, when
+                                              lon_w >= lon_e (a box across 0), lam >= lon_w or lam < lon_e */
+} rwrt_summary_regions;                    /* 264 bytes */
+
+/* Row layouts (dense, tails, row blocks) and their argument rules are those
+ * of rwrt_ray_density.  d_ray[nray] (int64): ray j of the call accumulates
+ * into column d_ray[j] (a shard's rays in the whole set's arrays), NULL:
+ * column j; a ray whose column is outside [0, nacc_cols) is skipped.  reg
+ * NULL: no boxes.  One lane walks one ray; no atomics.  Asynchronous and
+ * ordered on `stream`; needs no rwrt_ctx.  nray == 0 is a no-op. */
+rwrt_status rwrt_ray_summary(int64_t nray, int32_t it_begin, int32_t it_end,
+                             const double* d_rows, const int32_t* d_row_slot,
+                             const int32_t* d_tail_from, const double* d_tail_row,
+                             const int64_t* d_ray, int64_t nacc_cols,
+                             const rwrt_summary_regions* reg,
+                             double* d_f64, int32_t* d_i32, void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

@@ -20,7 +20,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_mercator_point", "rwrt_rhs", "rwrt_dp54_attempt",
                "rwrt_ray_initial", "rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails",
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
-               "rwrt_rk4_run", "rwrt_ray_density",
+               "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary",
                "rwrt_bs_ready", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
                "rwrt_rk45_run_tv_slots", "rwrt_rhs_tv",
                "rwrt_kat_rk45", "rwrt_selftest_math", "rwrt_host_fill_rows")
@@ -61,6 +61,16 @@ class DensityMap(ctypes.Structure):
                 ("lat0", ctypes.c_double), ("inv_dlat", ctypes.c_double)]
 
 
+SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
+
+
+class SummaryRegions(ctypes.Structure):
+    """``rwrt_summary_regions``: the lon-lat boxes of a ``rwrt_ray_summary`` call
+    (radians: lon_w, lon_e, lat_s, lat_n)."""
+    _fields_ = [("nreg", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("box", (ctypes.c_double * 4) * SUMMARY_MAXREG)]
+
+
 _lib = None
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -81,6 +91,7 @@ def load():
     lib.rwrt_last_error.restype = ctypes.c_char_p
     G, Pr, B = ctypes.POINTER(Grid), ctypes.POINTER(Params), ctypes.POINTER(Background)
     M = ctypes.POINTER(DensityMap)
+    R = ctypes.POINTER(SummaryRegions)
     sig = {
         "rwrt_pack_fields": [G, _P, _P, _P],
         "rwrt_mercator_point": [G, _P, _I64, _P, _P, _P, _P],
@@ -98,6 +109,7 @@ def load():
         "rwrt_expand_slots": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P],
         "rwrt_rk4_run": [_P, G, _P, _I64, Pr, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_density": [M, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
+        "rwrt_ray_summary": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, R, _P, _P, _P],
         "rwrt_bs_ready": [_I32, _I32, _P, _P, _P, _D, _D, _P, _P, _I32, _P],
         "rwrt_rk45_init_tv": [G, B, _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
         "rwrt_rk45_run_tv": [_P, G, B, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],

@@ -155,8 +155,8 @@ class WR:
     def _core_ray_run_hip(self, method, group=None, sink=None):
         """Shared driver of the two GPU ray loops.
 
-        ``sink`` (``ray_density``): a device-side consumer of the rows (the
-        engine's ``sink`` protocol, with ``take(idx)`` for a rank's shard)
+        ``sink`` (``ray_density``, ``ray_summary``): a device-side consumer of
+        the rows (the engine's ``sink`` protocol, with ``take(idx)`` for a rank's shard)
         that replaces the delivery into the history arrays -- no row reaches
         the host and the arrays keep only row 0.
 
@@ -285,6 +285,48 @@ class WR:
         if group is not None and shard.collective(world):
             dmap.allreduce(group)
         return dmap
+
+    def ray_summary(self, regions=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
+        """Initialise and integrate all rays like ``ray_run``, but reduce every
+        ray's rows to a path summary on the GPU (summary.py) instead of
+        delivering the history: returns the ``summary.RaySummary``, whose
+        ``numpy()`` gives fields of shape ``(3, nsource, nzwn)`` -- path
+        length, turning points, latitude range, first / last point, and per
+        region the first row inside and the rows spent there; only row 0 of
+        ``rlon .. rvg`` is filled.
+
+        ``regions``: up to 8 boxes ``(lon_w, lon_e, lat_s, lat_n)`` in degrees
+        (``lon_w > lon_e``: across 0).  ``mode='numpy'`` integrates on the GPU
+        all the same, delivers the history and applies
+        ``summary.reference_summary`` on the host (small runs; the
+        ``RaySummary`` returned holds its fields).  With a process ``group`` every rank ends with every ray's
+        summary."""
+        import summary as Sm
+        shape = (3, self.nsource, self.nzwn)
+        nray = 3 * self.nsource * self.nzwn
+        if mode == "numpy":
+            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
+            rows = np.full((nray, self.nt, 8), np.nan)
+            for c, h in enumerate((self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)):
+                rows[:, :, c] = h.reshape(self.nt, nray).T
+            rs = Sm.RaySummary.from_fields(Sm.reference_summary(rows, regions), self.nt, regions or (),
+                                           self.bs.engine().device)
+            rs.shape = shape
+            return rs
+        key = mode + "_rk45" if inte_method == "rk45" else mode
+        if key not in SUPPORTED:
+            self.core_ray_run(key)     # raises before any work
+        self.ray_initial(mode=mode, root_method=root_method)
+        import shard
+        world = shard.world_info(group)[1] if group is not None else 1
+        rs = Sm.RaySummary(nray, regions or (), self.bs.engine().device)
+        rs.shape = shape
+        # row 0 on every rank: the rank that integrates a ray carries it into row 1
+        rs.start(self.rlon[0], self.rlat[0], self.rmwn[0], self.ramp[0])
+        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=Sm.SummarySink(rs))
+        if group is not None and shard.collective(world):
+            rs.allreduce(group)
+        return rs
 
     def core_ray_run(self, mode="hip_rk45", group=None):
         if mode not in SUPPORTED:
