@@ -36,8 +36,9 @@ extern "C" {
 #define RWRT_ABI_VERSION 5  /* 3: constant row tails (rwrt_rk45_run_tails, rwrt_expand_tails);
                                4: row blocks for the live rays only (rwrt_rk45_run_slots);
                                5: ray-density maps binned on the device (rwrt_ray_density);
-                                  per-ray path summaries (rwrt_ray_summary) joined ABI 5 later as
-                                  an additive member: no earlier signature or layout changed */
+                                  per-ray path summaries (rwrt_ray_summary) and the wavenumber
+                                  map (rwrt_wn_map, rwrt_wn_fill) joined ABI 5 later as additive
+                                  members: no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -182,6 +183,47 @@ rwrt_status rwrt_ray_initial(const rwrt_grid* g, const double* d_packed,
                              const double* d_src_lat, const double* d_src_cos,
                              int32_t nzwn, const double* d_zwn, double* d_rows,
                              int32_t* d_info, void* stream);
+
+/* The wavenumber map (ABI 5, additive): the reference's WN (wn.py) on every
+ * grid node of nlev packed fp64 levels and for every zonal wavenumber -- the
+ * meridional wavenumbers the t = 0 dispersion relation admits, how many there
+ * are, and their group velocities.
+ *  d_packed [nlev][g->ncol][g->nrow][12] fp64; level_stride, in doubles, is
+ *    the distance between two levels (ignored when nlev == 1).
+ *  nlon <= g->ncol map columns (the cyclic pad column is no map column);
+ *    d_lon[nlon], d_lat[g->nrow]: the BS radian axes themselves (bs.lon,
+ *    bs.lat: float32-rounded, not lon0 + i*dlon); d_cos[g->nrow] = np.cos of
+ *    d_lat from the host libm; d_zwn[4][nzwn] as for the initial rays.
+ *  d_mwn, d_ug, d_vg [nlev][nlon][nrow][nzwn][3], d_rootnum
+ *    [nlev][nlon][nrow][nzwn] (int32).
+ * The entry (lev, i, j, iz, slot) is, bit for bit, what the initial-ray call
+ * above writes on level lev for a source at (d_lon[i], d_lat[j]): d_rows[3],
+ * [5], [6] at [slot][s][iz] -- the same device functions (csrc/ray_point.h)
+ * serve both, the field lookup included (the bilinear lookup at the node, not
+ * a read of the node's record).  rootnum counts the non-NaN slots of mwn (after the |m| > 100
+ * filter); ug, vg are NaN where a slot has no root; k == 0 gives rootnum 0 and
+ * ug = vg = 0.  d_info[1] (int32, zeroed by this call) counts polynomials with
+ * non-finite coefficients or a failed solve; rootnum is -1 and the nine values
+ * are NaN there (the pole rows of a lat-lon grid), and nothing raises.
+ * One thread per (level, node, k).  Asynchronous and ordered on `stream`;
+ * needs no rwrt_ctx. */
+rwrt_status rwrt_wn_map(const rwrt_grid* g, const double* d_packed, int32_t nlev,
+                        int64_t level_stride, int32_t nlon, const double* d_lon,
+                        const double* d_lat, const double* d_cos, int32_t nzwn,
+                        const double* d_zwn, double* d_mwn, double* d_ug,
+                        double* d_vg, int32_t* d_rootnum, int32_t* d_info,
+                        void* stream);
+
+/* NaN fill of one level of a map (the reference WN's postprocess, defined in
+ * csrc/wn_fill.h): d_in, d_out [nlon][nlat][nplane], nplane = nzwn * 3.  A
+ * non-NaN entry is copied; a NaN entry becomes the mean of the non-NaN ones
+ * among its eight neighbours in the same plane of d_in (i +- 1 wraps when
+ * cyclic, is skipped at the edge otherwise; j +- 1 is skipped at the edge;
+ * summed with di = -1, 0, 1 outer, dj = -1, 0, 1 inner; infinities count), and
+ * stays NaN when there is none.  d_out == d_in is an argument error. */
+rwrt_status rwrt_wn_fill(int32_t nlon, int32_t nlat, int32_t nplane, int32_t cyclic,
+                         const double* d_in, double* d_out, void* stream);
+
 /* Solver construction: RungeKutta.__init__ (rkf45.py:335-366) with
  * select_initial_step (rkf45.py:34-99) on d_y0[5][nray].
  * Writes d_state[12][nray] = y f t(=0) h_abs, zeroes d_count[nray][2]

@@ -5,7 +5,8 @@ The modules of this directory mirror the reference's flat layout (``main_wr``,
 this directory on ``sys.path`` and ``from wr import WR``.  ``engine`` and
 ``_hip`` are the device layer (librwrt.so through ctypes).  ``density`` bins
 ray points into lon-lat maps on the GPU and ``summary`` reduces every ray's
-rows to a path summary there; their names are exported here too.
+rows to a path summary there; ``wn.WN`` maps the admissible meridional
+wavenumbers of every grid node there; their names are exported here too.
 """
 import os
 import sys
@@ -16,7 +17,8 @@ if _here not in sys.path:
 
 _DENSITY = ["DensitySpec", "DensityMap", "DensitySink", "reference_bins"]
 _SUMMARY = ["RaySummary", "SummarySink", "Tee", "reference_summary"]
-__all__ = _DENSITY + _SUMMARY
+_WN = ["WN", "reference_wn_map", "reference_fill"]
+__all__ = _DENSITY + _SUMMARY + _WN
 
 
 def __getattr__(name):
@@ -27,4 +29,7 @@ def __getattr__(name):
     if name in _SUMMARY:
         import summary
         return getattr(summary, name)
+    if name in _WN:
+        import wn
+        return getattr(wn, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

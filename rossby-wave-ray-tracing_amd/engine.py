@@ -159,6 +159,7 @@ class RayEngine:
             raise ValueError(f"fields must be [ncol, nrow, {H.NFIELD_REF}], got {tuple(f.shape)}")
         f = f.to(self.device).contiguous()
         self.grid = grid_of(lon, lat, f.shape[0])
+        self.lon, self.lat = np.array(lon, np.float64), np.array(lat, np.float64)
         self.packed = torch.empty((f.shape[0], f.shape[1], H.NFIELD_PACK), dtype=F64,
                                   device=self.device)
         H.check(H.load().rwrt_pack_fields(self.grid, H.dptr(f), H.dptr(self.packed), self._stream()))
@@ -208,6 +209,7 @@ class RayEngine:
         self = cls.__new__(cls)
         self.device = levels.device
         self.grid = levels.grid
+        self.lon, self.lat = levels.lon, levels.lat
         self.levels = levels
         self.work = torch.zeros(4, dtype=torch.int32, device=self.device)
         if levels.nlev == 1 and not levels.fp32 and not time_varying:
@@ -225,6 +227,7 @@ class RayEngine:
         self = cls.__new__(cls)
         self.device = packed.device
         self.grid = grid_of(lon, lat, packed.shape[0])
+        self.lon, self.lat = np.array(lon, np.float64), np.array(lat, np.float64)
         self.packed = packed.contiguous()
         self.work = torch.zeros(4, dtype=torch.int32, device=self.device)
         return self
@@ -327,6 +330,64 @@ class RayEngine:
                 f"Array must not contain infs or NaNs ({int(info.item())} dispersion "
                 f"polynomials with non-finite coefficients; np.roots raises here too)")
         return rows
+
+    # ----------------------------------------------------- wavenumber map
+    levels = None   # the levels.Levels of an engine built from_levels
+
+    def wn_map(self, zwn, freq, levels=None, nlon=None):
+        """The wavenumber map (rwrt_wn_map): the initial rays of every grid node,
+        device tensors ``(mwn, ug, vg, rootnum, info)`` -- ``mwn, ug, vg``
+        ``[nlon, nlat, nzwn, 3]``, ``rootnum [nlon, nlat, nzwn]`` (int32: the
+        roots a ray launched at the node starts with, -1 where ``np.roots``
+        would raise) and ``info[1]``, the number of -1 entries.  Nothing raises
+        and the results are not waited for.
+
+        ``levels``: for an engine built ``from_levels``, a ``range`` of level
+        indices (step 1), mapped in one call; the outputs then lead with a
+        level axis.  None: the static state, or level 0, without that axis.
+        ``nlon``: map columns (default: every longitude; never the cyclic pad
+        column)."""
+        nx = len(self.lon) if nlon is None else int(nlon)
+        if not 1 <= nx <= len(self.lon):
+            raise ValueError(f"nlon must be 1..{len(self.lon)}, got {nlon}")
+        if self.levels is not None and self.levels.fp32:
+            raise NotImplementedError("wavenumber maps need fp64 level storage")
+        if levels is None:
+            packed = self.packed if self.levels is None else self.levels.packed[0]
+            nlev, stride = 1, 0
+        else:
+            if self.levels is None:
+                raise ValueError("levels needs an engine built from_levels")
+            levels = range(*levels) if isinstance(levels, tuple) else levels
+            if not isinstance(levels, range) or levels.step != 1 or len(levels) < 1 \
+                    or levels.start < 0 or levels.stop > self.levels.nlev:
+                raise ValueError(f"levels must be a range (step 1) within 0..{self.levels.nlev}, got {levels!r}")
+            packed = self.levels.packed[levels.start]
+            nlev, stride = len(levels), self.levels.packed.stride(0)
+        ny, nz = len(self.lat), len(zwn)
+        lead = () if levels is None else (nlev,)
+        mwn, ug, vg = (torch.empty(lead + (nx, ny, nz, 3), dtype=F64, device=self.device) for _ in range(3))
+        rootnum = torch.empty(lead + (nx, ny, nz), dtype=torch.int32, device=self.device)
+        info = torch.zeros(1, dtype=torch.int32, device=self.device)
+        ax = torch.as_tensor(np.concatenate([self.lon[:nx], self.lat, np.cos(self.lat)]), dtype=F64).to(self.device)
+        zc = self.zwn_tensor(zwn, freq)
+        H.check(H.load().rwrt_wn_map(self.grid, H.dptr(packed, F64, "packed levels"), nlev, stride, nx,
+                                     ax.data_ptr(), ax[nx:].data_ptr(), ax[nx + ny:].data_ptr(), nz, H.dptr(zc),
+                                     H.dptr(mwn), H.dptr(ug), H.dptr(vg), H.dptr(rootnum), H.dptr(info),
+                                     self._stream()))
+        return mwn, ug, vg, rootnum, info
+
+    def wn_fill(self, a, cyclic):
+        """The map's NaN fill (rwrt_wn_fill, wn.reference_fill) of a device
+        tensor ``[(nlev,) nlon, nlat, nzwn, 3]``: a new tensor."""
+        a = a.contiguous()
+        out = torch.empty_like(a)
+        src, dst = (a, out) if a.ndim == 5 else (a[None], out[None])
+        nx, ny = src.shape[1], src.shape[2]
+        for lev in range(src.shape[0]):
+            H.check(H.load().rwrt_wn_fill(nx, ny, src[lev].numel() // (nx * ny), int(bool(cyclic)),
+                                          src[lev].data_ptr(), dst[lev].data_ptr(), self._stream()))
+        return out
 
     # ------------------------------------------------------------ ray loop
     @staticmethod
