@@ -38,7 +38,8 @@ extern "C" {
                                5: ray-density maps binned on the device (rwrt_ray_density);
                                   per-ray path summaries (rwrt_ray_summary) and the wavenumber
                                   map (rwrt_wn_map, rwrt_wn_fill) joined ABI 5 later as additive
-                                  members: no earlier signature or layout changed */
+                                  members, and so did the spherical-harmonic filter
+                                  (rwrt_sh_filter): no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -223,6 +224,34 @@ rwrt_status rwrt_wn_map(const rwrt_grid* g, const double* d_packed, int32_t nlev
  * stays NaN when there is none.  d_out == d_in is an argument error. */
 rwrt_status rwrt_wn_fill(int32_t nlon, int32_t nlat, int32_t nplane, int32_t cyclic,
                          const double* d_in, double* d_out, void* stream);
+
+/* Triangular spherical-harmonic truncation of a batch of fields (the
+ * reference's SHSF.py, NCL's shaec -> tri_trunc -> shsec; the definition is
+ * shsf.reference_filter, the weights and Legendre recurrence are
+ * csrc/shsf_legendre.h).  Grid: nlat odd, latitudes equally spaced from -pi/2
+ * to +pi/2 with both poles, ascending; nlon even, longitudes 2 pi i / nlon.
+ *  d_in [nfield][nlat][nlon] float32, file layout.
+ *  d_w [nlat]: the Clenshaw-Curtis weights in x = sin(lat) (they sum to 2).
+ *  d_x [2][nlat]: sin(lat), then cos(lat) (exactly 0 at the poles), from the host.
+ *  d_spec [nfield][trunc+1][trunc+1][2]: the coefficients a_lm (re, im) at
+ *    [l][m], a_lm = sum_j w_j p_lm(x_j) F_m(j) with F_m the unnormalised
+ *    longitude DFT and int p_lm^2 dx = 1; zero for l < m and for orders above
+ *    min(trunc, nlon/2 - 1).  Always written.
+ *  d_out32, d_out64 [nfield][nlat][nlon] or NULL: the field rebuilt from the
+ *    degrees l <= trunc, fp64 and/or that value rounded to float32; both NULL:
+ *    coefficients only.
+ *  d_scratch: 2*nfield*(trunc+1)*nlat*2 doubles.
+ * RWRT_ERR_ARG: nlat even or < 3, nlon odd, trunc < 0 or > (nlat-1)/2,
+ * nfield < 0 (or > 65535), any two of d_in, d_out32, d_out64 overlapping, a
+ * NULL buffer, or a row (nlon) or an order (trunc) too large for LDS.
+ * nfield == 0 is a no-op.  Every sum has a fixed order (no atomics): a call's
+ * output is bit-identical from call to call, and a field's result does not
+ * depend on the batch it is in.  Four kernels, asynchronous and ordered on
+ * `stream`; needs no rwrt_ctx. */
+rwrt_status rwrt_sh_filter(int32_t nlon, int32_t nlat, int32_t nfield, int32_t trunc,
+                           const float* d_in, const double* d_w, const double* d_x,
+                           double* d_spec, float* d_out32, double* d_out64,
+                           double* d_scratch, void* stream);
 
 /* Solver construction: RungeKutta.__init__ (rkf45.py:335-366) with
  * select_initial_step (rkf45.py:34-99) on d_y0[5][nray].

@@ -50,17 +50,32 @@ class BS:
         return self.lat
 
     # ---------------------------------------------------------------- input
-    def loadbs_ncfile(self, ncfile):
-        """Read ``u, v`` (+ ``lat``/``lon`` if present) from a netCDF-3 or .npz file."""
+    def loadbs_ncfile(self, ncfile, trunc=None):
+        """Read ``u, v`` (+ ``lat``/``lon`` if present) from a netCDF-3 or .npz file.
+        ``trunc``: as in ``load_arrays``."""
         d = ncio.read(ncfile)
         lat = next((d[k] for k in ("lat", "latitude", "Lat", "Latitude") if k in d), None)
         lon = next((d[k] for k in ("lon", "longitude", "Lon", "Longitude") if k in d), None)
-        self.load_arrays(d["u"], d["v"], lat, lon)
+        self.load_arrays(d["u"], d["v"], lat, lon, trunc=trunc)
 
-    def load_arrays(self, u, v, lat=None, lon=None):
-        """``loadbs_ncfile`` on in-memory arrays: ``u, v`` as ``(nlat, nlon)``, degrees."""
+    def load_arrays(self, u, v, lat=None, lon=None, trunc=None):
+        """``loadbs_ncfile`` on in-memory arrays: ``u, v`` as ``(nlat, nlon)``, degrees.
+
+        ``trunc`` (default None: nothing changes, no GPU is touched): ``u, v``
+        are truncated at spherical-harmonic degree ``trunc`` on the GPU right
+        after reading (``shsf.SHFilter``, the reference's ``SHSF.py``) -- in
+        the file's own latitude order, before the descending-latitude rule
+        below.  Raises ``ValueError`` when the axes are not the filter's grid
+        (``shsf.check_grid``)."""
         u = np.array(u, dtype=self.all_dtype)
         v = np.array(v, dtype=self.all_dtype)
+        if trunc is not None:
+            import shsf
+            shsf.check_grid(self.nlat, self.nlon, lat)
+            if u.shape != (self.nlat, self.nlon) or v.shape != (self.nlat, self.nlon):
+                raise ValueError(f"u, v must be [{self.nlat}, {self.nlon}]")
+            uv = shsf.shared_filter(self.nlat, self.nlon, trunc).filter(np.stack([u, v])).cpu().numpy()
+            u, v = uv[0].astype(self.all_dtype), uv[1].astype(self.all_dtype)
         if lat is not None:
             lat = np.array(lat, dtype=self.all_dtype)
             self.lat[:] = (lat * pi / 180).astype(self.all_dtype_)   # float32 arithmetic

@@ -51,6 +51,7 @@ class Levels:
         if not (lat_deg[0] < lat_deg[-1]):
             raise ValueError("Levels needs an ascending latitude axis (flip u, v, lat first)")
         self.nlat, self.nlon = len(lat_deg), len(lon_deg)
+        self.lat_deg, self._filters = lat_deg, {}
         # the axes exactly as BS.loadbs_ncfile builds them (float32 arithmetic)
         b = BS(self.nlon, self.nlat)
         b.load_arrays(np.zeros((self.nlat, self.nlon), np.float32),
@@ -73,13 +74,20 @@ class Levels:
         from engine import grid_of
         return grid_of(self.lon, self.lat, self.nlon + 1)
 
-    def set_level(self, j, u, v):
+    def set_level(self, j, u, v, trunc=None):
         """Build level ``j`` from ``u, v[nlat, nlon]`` (float32, file layout; host
-        arrays or device tensors) with ``rwrt_bs_ready`` (asynchronous)."""
+        arrays or device tensors) with ``rwrt_bs_ready`` (asynchronous).
+        ``trunc``: first truncate ``u, v`` at that spherical-harmonic degree
+        (``shsf.SHFilter``, one two-field batch; nothing leaves the device)."""
         u = torch.as_tensor(u, dtype=torch.float32).to(self.device).contiguous()
         v = torch.as_tensor(v, dtype=torch.float32).to(self.device).contiguous()
         if u.shape != (self.nlat, self.nlon) or v.shape != (self.nlat, self.nlon):
             raise ValueError(f"u, v must be [{self.nlat}, {self.nlon}]")
+        if trunc is not None:
+            u, v = self.sh_filter(trunc).filter(torch.stack([u, v]))
+        self._ready(j, u, v)
+
+    def _ready(self, j, u, v):
         H.check(H.load().rwrt_bs_ready(self.nlon, self.nlat, H.dptr(u), H.dptr(v),
                                        H.dptr(self.trig), self.dx, self.dy, H.dptr(self.scratch),
                                        self.packed[j].data_ptr(), int(self.fp32), H.stream(self.device)))
@@ -88,6 +96,29 @@ class Levels:
                                            H.dptr(self.trig), self.dx, self.dy,
                                            H.dptr(self.scratch), self.level0_f64.data_ptr(), 0,
                                            H.stream(self.device)))
+
+    def set_levels(self, u, v, trunc=None):
+        """Build every level from ``u, v[nlev, nlat, nlon]``; with ``trunc`` the
+        whole batch of ``2 nlev`` fields is filtered in one call first."""
+        u = torch.as_tensor(u, dtype=torch.float32).to(self.device).contiguous()
+        v = torch.as_tensor(v, dtype=torch.float32).to(self.device).contiguous()
+        shape = (self.nlev, self.nlat, self.nlon)
+        if u.shape != shape or v.shape != shape:
+            raise ValueError(f"u, v must be [{self.nlev}, {self.nlat}, {self.nlon}]")
+        if trunc is not None:
+            u, v = self.sh_filter(trunc).filter(torch.stack([u, v]))
+        for j in range(self.nlev):
+            self._ready(j, u[j], v[j])
+
+    def sh_filter(self, trunc):
+        """The ``shsf.SHFilter`` of this grid at ``trunc`` (kept).  Raises
+        ``ValueError`` when the axes are not the filter's grid."""
+        import shsf
+        trunc = int(trunc)
+        if trunc not in self._filters:
+            shsf.check_grid(self.nlat, self.nlon, self.lat_deg)
+            self._filters[trunc] = shsf.SHFilter(self.nlat, self.nlon, trunc, self.device)
+        return self._filters[trunc]
 
     def background(self):
         """The ``rwrt_background`` description of these levels."""
