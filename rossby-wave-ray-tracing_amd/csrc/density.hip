@@ -18,14 +18,11 @@
 #include <string>
 
 #include "rwrt.h"
+#include "abi_host.h"
 #include "density_bins.h"
+#include "launch_rows.h"
 
 namespace rwrt {
-
-// (defined in rwrt.hip: the calling thread's last error, rwrt_last_error)
-rwrt_status fail(rwrt_status s, const char* fmt, const char* detail);
-rwrt_status check_launch(const char* what);
-
 namespace {
 
 struct DensityRun {
@@ -61,51 +58,29 @@ __device__ __forceinline__ void density_point(DensityRun& r, const rwrt_density_
 
 constexpr int kDensityBatch = 4;   // rows loaded ahead per lane
 
+struct DensityRow {   // what the lane needs of a row: lon lat, and the weight column
+  double2 p;
+  double w;
+};
+
 __global__ void __launch_bounds__(256)
 ray_density_kernel(const rwrt_density_map m, int64_t nray, int32_t it_begin, int32_t it_end,
                    const double* __restrict__ rows, const int32_t* __restrict__ row_slot,
                    const int32_t* __restrict__ tail_from, const double* __restrict__ tail_row,
                    const int32_t* __restrict__ chan, unsigned long long* __restrict__ count,
                    double* __restrict__ wsum) {
-  const int32_t nrows = it_end - it_begin;
+  const LaunchRows L{rows, row_slot, tail_from, tail_row, it_begin, it_end};
   const int wc = (m.wcol >= 0) ? m.wcol : 0;   // (a column that exists: its value is unused without a weight)
   for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < nray; j += (int64_t)gridDim.x * blockDim.x) {
     const int32_t c = chan ? chan[j] : 0;
     if (c < 0 || c >= m.nchan) continue;
-    // rows [it_begin, tf) are read from the ray's block, rows [tf, it_end) are its tail
-    int32_t tf = it_end;
-    if (tail_from) tf = min(max(tail_from[j], it_begin), it_end);
-    int64_t blk = j;
-    if (row_slot) {
-      blk = row_slot[j];
-      if (blk < 0) tf = it_begin;   // no block: every row is the tail
-    }
     DensityRun run;
-    const int32_t nread = tf - it_begin;
-    if (nread > 0) {
-      const double* __restrict__ r = rows + blk * (int64_t)nrows * RWRT_NOUT;
-      int32_t i = 0;
-      for (; i + kDensityBatch <= nread; i += kDensityBatch) {
-        double2 p[kDensityBatch];
-        double w[kDensityBatch];
-#pragma unroll
-        for (int k = 0; k < kDensityBatch; ++k) {
-          p[k] = *reinterpret_cast<const double2*>(r + (int64_t)(i + k) * RWRT_NOUT);
-          w[k] = r[(int64_t)(i + k) * RWRT_NOUT + wc];
-        }
-#pragma unroll
-        for (int k = 0; k < kDensityBatch; ++k) density_point(run, m, p[k].x, p[k].y, w[k], c, 1, count, wsum);
-      }
-      for (; i < nread; ++i) {
-        const double2 p = *reinterpret_cast<const double2*>(r + (int64_t)i * RWRT_NOUT);
-        density_point(run, m, p.x, p.y, r[(int64_t)i * RWRT_NOUT + wc], c, 1, count, wsum);
-      }
-    }
-    if (tf < it_end) {
-      const double* __restrict__ t = tail_row + j * RWRT_NOUT;
-      const double2 p = *reinterpret_cast<const double2*>(t);
-      density_point(run, m, p.x, p.y, t[wc], c, (unsigned long long)(it_end - tf), count, wsum);
-    }
+    launch_rows_walk<kDensityBatch, DensityRow>(
+        L, j, [wc](const double* r) { return DensityRow{*reinterpret_cast<const double2*>(r), r[wc]}; },
+        [&](int32_t, const DensityRow& v) { density_point(run, m, v.p.x, v.p.y, v.w, c, 1, count, wsum); },
+        [&](int32_t, int32_t n, const DensityRow& v) {
+          density_point(run, m, v.p.x, v.p.y, v.w, c, (unsigned long long)n, count, wsum);
+        });
     density_flush(run, m.wcol >= 0, count, wsum);
   }
 }
@@ -133,17 +108,11 @@ extern "C" rwrt_status rwrt_ray_density(const rwrt_density_map* m, int64_t nray,
     return fail(RWRT_ERR_ARG, "rwrt_ray_density: inv_dlat must be finite and positive%s", "");
   if (!std::isfinite(m->lat0)) return fail(RWRT_ERR_ARG, "rwrt_ray_density: lat0 must be finite%s", "");
   if (m->wcol >= 0 && !d_wsum) return fail(RWRT_ERR_ARG, "rwrt_ray_density: wcol >= 0 needs d_wsum%s", "");
-  if (it_end <= it_begin) return fail(RWRT_ERR_ARG, "rwrt_ray_density: need it_begin < it_end%s", "");
-  if (nray < 0 || nray > 0x7fffffffLL) return fail(RWRT_ERR_ARG, "rwrt_ray_density: nray out of range%s", "");
-  if (!d_tail_from != !d_tail_row)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_density: tails need both d_tail_from and d_tail_row%s", "");
-  if (d_row_slot && !d_tail_from)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_row_slot needs tails (d_tail_from, d_tail_row)%s", "");
+  if (const rwrt_status st = check_launch_rows("rwrt_ray_density", nray, it_begin, it_end, d_rows, d_row_slot,
+                                               d_tail_from, d_tail_row))
+    return st;
   if (!d_count) return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_count is NULL%s", "");
   if (nray == 0) return RWRT_OK;
-  if (!d_rows) return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_rows is NULL%s", "");
-  if (reinterpret_cast<uintptr_t>(d_rows) % 16 != 0 || reinterpret_cast<uintptr_t>(d_tail_row) % 16 != 0)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_rows and d_tail_row must be 16-byte aligned%s", "");
   const unsigned blocks = (unsigned)((nray + 255) / 256);
   hipLaunchKernelGGL(ray_density_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *m, nray, it_begin,
                      it_end, d_rows, d_row_slot, d_tail_from, d_tail_row, d_chan,

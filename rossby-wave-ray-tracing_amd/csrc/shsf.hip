@@ -22,14 +22,10 @@
 #include <cstdint>
 
 #include "rwrt.h"
+#include "abi_host.h"
 #include "shsf_legendre.h"
 
 namespace rwrt {
-
-// (defined in rwrt.hip: the calling thread's last error, rwrt_last_error)
-rwrt_status fail(rwrt_status s, const char* fmt, const char* detail);
-rwrt_status check_launch(const char* what);
-
 namespace {
 
 constexpr int kShThreads = 256;

@@ -17,14 +17,12 @@
 #include <cstdint>
 
 #include "rwrt.h"
+#include "abi_host.h"
 #include "ray_point.h"
 #include "wn_fill.h"
 
 namespace rwrt {
 
-// (defined in rwrt.hip: the calling thread's last error, rwrt_last_error)
-rwrt_status fail(rwrt_status s, const char* fmt, const char* detail);
-rwrt_status check_launch(const char* what);
 // (defined in rwrt.hip: the conditions of a packed level)
 rwrt_status make_field(const rwrt_grid* g, const double* packed, Field& F);
 

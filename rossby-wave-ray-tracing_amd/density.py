@@ -19,6 +19,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 import _hip as H
+from launch_rows import RowSink, one_row, row_args
 
 WEIGHT_COLUMNS = {"k": 2, "l": 3, "amp": 4, "ug": 5, "vg": 6}   # columns of the 8-column output row
 TWO_PI = 2 * math.pi
@@ -150,36 +151,22 @@ class DensityMap:
         each ray's channel (int32 device tensor; None: channel 0).  One
         asynchronous ``rwrt_ray_density`` call on the device's current stream."""
         import torch
-        if slots is not None and tails is None:
-            raise ValueError("row slots need tails")
-        if view.ndim != 3 or view.shape[2] != H.NOUT or view.shape[1] != i1 - i0:
-            raise ValueError(f"rows must be [n, {i1 - i0}, {H.NOUT}], got {tuple(view.shape)}")
-        nray = int(slots.slot.numel() if slots is not None else view.shape[0])
-        if tails is not None and tails.frm.numel() != nray:
-            raise ValueError(f"tails of {tails.frm.numel()} rays for {nray} rays")
+        nray, rows = row_args(i0, i1, view, tails, slots)
         chan = self._chan(chan, nray)
         H.check(H.load().rwrt_ray_density(
-            self._c, nray, int(i0), int(i1), H.dptr(view, torch.float64, "rows"),
-            None if slots is None else H.dptr(slots.slot, torch.int32),
-            None if tails is None else H.dptr(tails.frm, torch.int32),
-            None if tails is None else H.dptr(tails.row, torch.float64),
-            H.dptr(chan, torch.int32), H.dptr(self.count, torch.int64), H.dptr(self.wsum),
-            H.stream(self.device)))
+            self._c, nray, int(i0), int(i1), *rows, H.dptr(chan, torch.int32), H.dptr(self.count, torch.int64),
+            H.dptr(self.wsum), H.stream(self.device)))
 
     def add_points(self, lon, lat, w=None, chan=None):
         """Bin single points (radians): the same entry point on a ``[n, 1, 8]``
         row tensor.  Used for row 0 (the initial rays), which sinks never
         receive."""
-        import torch
-        lon = torch.as_tensor(lon, dtype=torch.float64).reshape(-1)
-        rows = torch.zeros((lon.numel(), 1, H.NOUT), dtype=torch.float64, device=self.device)
-        rows[:, 0, 0] = lon.to(self.device)
-        rows[:, 0, 1] = torch.as_tensor(lat, dtype=torch.float64).reshape(-1).to(self.device)
+        cols = {0: lon, 1: lat}
         if self.spec.wcol >= 0:
             if w is None:
                 raise ValueError(f"the map sums {self.spec.weight!r}: pass w")
-            rows[:, 0, self.spec.wcol] = torch.as_tensor(w, dtype=torch.float64).reshape(-1).to(self.device)
-        self.add_rows(0, 1, rows, chan=chan)
+            cols[self.spec.wcol] = w
+        self.add_rows(0, 1, one_row(cols, self.device), chan=chan)
 
     def allreduce(self, group=None):
         """SUM of the maps of every rank of ``group`` (``torch.distributed.all_reduce``
@@ -230,44 +217,20 @@ class DensityMap:
         ncio.write(ncfile, dims, v)
 
 
-class DensitySink:
+class DensitySink(RowSink):
     """A ``sink`` of ``RayEngine.integrate`` / ``integrate_rk4`` / ``resume``
-    (``(i0, i1, view, tails=None, slots=None)``) and of ``shard.run_sharded``
-    (``(i0, i1, rows, idx, tails=None, slots=None)``) that bins each launch's
-    rows into ``map`` where they lie: it takes row blocks and tails as they
-    are, enqueues on the engine's stream (so the alternating row buffers need
-    no extra events) and copies nothing to the host.  ``chan``: each ray's
-    channel (length nray; with ``run_sharded`` indexed by the shard's ``idx``)."""
-    takes_tails = True
-    takes_slots = True
+    and of ``shard.run_sharded`` (``launch_rows.RowSink``) that bins each
+    launch's rows into ``map``.  ``chan``: each ray's channel (length nray;
+    with ``run_sharded`` indexed by the shard's ``idx``; None: channel 0)."""
 
     def __init__(self, map, chan=None):
+        super().__init__(map, None if chan is None else map._chan(chan, len(chan)))
         self.map = map
-        self.chan = None if chan is None else map._chan(chan, len(chan))
-        self._sub = (None, None)   # (idx, chan[idx]) of the last shard
 
-    def take(self, idx):
-        """The sink of the rays ``idx`` (a shard integrated on its own)."""
-        import torch
-        if self.chan is None:
-            return self
-        idx = torch.as_tensor(idx, device=self.map.device).to(torch.int64)
-        return DensitySink(self.map, self.chan[idx])
+    chan = property(lambda self: self.per_ray)
 
-    def __call__(self, i0, i1, view, *rest, tails=None, slots=None):
-        import torch
-        chan = self.chan
-        if rest and (torch.is_tensor(rest[0]) or isinstance(rest[0], np.ndarray)):
-            idx, rest = rest[0], rest[1:]   # the sharded form: this shard's ray indices
-            if chan is not None:
-                if self._sub[0] is not idx:
-                    self._sub = (idx, chan[torch.as_tensor(idx, device=chan.device).to(torch.int64)].contiguous())
-                chan = self._sub[1]
-        if len(rest) > 0:
-            tails = rest[0]
-        if len(rest) > 1:
-            slots = rest[1]
-        self.map.add_rows(i0, i1, view, tails, slots, chan)
+    def select(self, idx):
+        return None if self.per_ray is None else self.per_ray[idx]
 
 
 def with_channels(spec, nchan):

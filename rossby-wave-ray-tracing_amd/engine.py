@@ -12,6 +12,7 @@ import torch
 
 import _hip as H
 from constants import rearth as R_EARTH
+from launch_rows import deliver   # (handing a launch's rows to a sink)
 
 F64 = torch.float64
 
@@ -109,19 +110,6 @@ class Slots:
                                            H.dptr(tails.frm, torch.int32), H.dptr(tails.row, F64),
                                            H.dptr(view, F64), H.dptr(d, F64), H.stream(self.slot.device)))
         return d
-
-
-def deliver(eng, sink, i0, i1, view, tails, slots=None):
-    """Hand a launch's rows to ``sink``: with its tails when the sink takes
-    them (``sink.takes_tails``), else dense (the tails expanded into ``view``);
-    row blocks (``slots``) go only to a sink that takes them."""
-    if slots is not None:
-        return sink(i0, i1, view, tails, slots)
-    if tails is not None and getattr(sink, "takes_tails", False):
-        return sink(i0, i1, view, tails)
-    if tails is not None:
-        eng.expand(view, tails, i0, i1)
-    return sink(i0, i1, view)
 
 
 class RayEngine:

@@ -328,7 +328,7 @@ def run_sharded(eng, y0, nt, tstep=7200.0, group=None, rank=None, world=None, pr
     and both global couplings are decided over every ray, so the union of the
     shards equals the single-GPU run bit for bit.
     """
-    from engine import t_eval_of
+    from engine import deliver, t_eval_of
     if rank is None:
         rank, world = world_info(group)
     p = eng.params(nt, tstep)
@@ -383,20 +383,8 @@ def run_sharded(eng, y0, nt, tstep=7200.0, group=None, rank=None, world=None, pr
             last["row"] = slots.last_row(rows, tails, i1)
         else:
             last["row"] = rows[:, -1] if tails is None else tails.last_row(rows, i1)
-        if sink is None:
-            return
-        if slots is not None:
-            if getattr(sink, "takes_slots", False):
-                return sink(i0, i1, rows, idx, tails, slots)
-            # (a sink that wants dense rows: the row blocks and tails expanded)
-            dense["buf"] = slots.dense(rows, tails, i0, i1, dense.get("buf"))
-            return sink(i0, i1, dense["buf"], idx)
-        if tails is not None and getattr(sink, "takes_tails", False):
-            sink(i0, i1, rows, idx, tails)
-        else:
-            if tails is not None:
-                eng.expand(rows, tails, i0, i1)   # (a sink that wants the rows dense)
-            sink(i0, i1, rows, idx)
+        if sink is not None:
+            deliver(eng, sink, i0, i1, rows, tails, slots, idx=idx, scratch=dense)
     keep.takes_tails = True
     keep.takes_slots = True
 

@@ -20,6 +20,7 @@ import math
 import numpy as np
 
 import _hip as H
+from launch_rows import RowSink, one_row, row_args
 
 R_EARTH = 6.3712e6      # metres: path_m = path * R_EARTH
 TWO_PI = 2 * math.pi
@@ -179,20 +180,10 @@ class RaySummary:
 
     def _update(self, i0, i1, view, tails, slots, ray):
         import torch
-        if slots is not None and tails is None:
-            raise ValueError("row slots need tails")
-        if view.ndim != 3 or view.shape[2] != H.NOUT or view.shape[1] != i1 - i0:
-            raise ValueError(f"rows must be [n, {i1 - i0}, {H.NOUT}], got {tuple(view.shape)}")
-        n = int(slots.slot.numel() if slots is not None else view.shape[0])
-        if tails is not None and tails.frm.numel() != n:
-            raise ValueError(f"tails of {tails.frm.numel()} rays for {n} rays")
+        n, rows = row_args(i0, i1, view, tails, slots)
         ray = self._ray(ray, n)
         H.check(H.load().rwrt_ray_summary(
-            n, int(i0), int(i1), H.dptr(view, torch.float64, "rows"),
-            None if slots is None else H.dptr(slots.slot, torch.int32),
-            None if tails is None else H.dptr(tails.frm, torch.int32),
-            None if tails is None else H.dptr(tails.row, torch.float64),
-            H.dptr(ray, torch.int64), self.nray, self._c,
+            n, int(i0), int(i1), *rows, H.dptr(ray, torch.int64), self.nray, self._c,
             H.dptr(self.f64, torch.float64), H.dptr(self.i32, torch.int32), H.stream(self.device)))
         return ray
 
@@ -202,12 +193,7 @@ class RaySummary:
         tensors (``RayEngine.initial_rows``) of any shape.  Does not claim the
         rays (``owned``): with a process group every rank starts every ray and
         integrates its own."""
-        import torch
-        cols = [torch.as_tensor(v, dtype=torch.float64).reshape(-1).to(self.device) for v in (lon0, lat0, l0, amp0)]
-        rows = torch.zeros((cols[0].numel(), 1, H.NOUT), dtype=torch.float64, device=self.device)
-        for col, v in zip((0, 1, 3, 4), cols):
-            rows[:, 0, col] = v
-        self._update(0, 1, rows, None, None, ray)
+        self._update(0, 1, one_row({0: lon0, 1: lat0, 3: l0, 4: amp0}, self.device), None, None, ray)
         return self
 
     @classmethod
@@ -315,52 +301,21 @@ class RaySummary:
         ncio.write(ncfile, dims, v)
 
 
-def _split_call(rest, tails, slots):
-    """The two call forms of a sink: ``(i0, i1, view[, tails[, slots]])`` and
-    the sharded ``(i0, i1, rows, idx[, tails[, slots]])`` -> (idx, tails, slots)."""
-    import torch
-    idx = None
-    if rest and (torch.is_tensor(rest[0]) or isinstance(rest[0], np.ndarray)):
-        idx, rest = rest[0], rest[1:]
-    if len(rest) > 0:
-        tails = rest[0]
-    if len(rest) > 1:
-        slots = rest[1]
-    return idx, tails, slots
-
-
-class SummarySink:
+class SummarySink(RowSink):
     """A ``sink`` of ``RayEngine.integrate`` / ``integrate_rk4`` / ``resume``
-    (``(i0, i1, view, tails=None, slots=None)``) and of ``shard.run_sharded``
-    (``(i0, i1, rows, idx, tails=None, slots=None)``) that updates ``summary``
-    from each launch's rows where they lie: row blocks and tails as they are,
-    enqueued on the engine's stream, nothing copied to the host.  ``ray``:
-    the column of each ray of the integration (``take``); the sharded form's
-    ``idx`` is that map."""
-    takes_tails = True
-    takes_slots = True
+    and of ``shard.run_sharded`` (``launch_rows.RowSink``) that updates
+    ``summary`` from each launch's rows.  ``ray``: the column of each ray of
+    the integration (None: ray j is column j); the sharded form's ``idx`` and
+    ``take(idx)`` select from it, or are the columns themselves."""
 
     def __init__(self, summary, ray=None):
+        super().__init__(summary, ray if ray is None else summary._ray(ray, len(ray)))
         self.summary = summary
-        self.ray = ray if ray is None else summary._ray(ray, len(ray))
-        self._sub = (None, None)   # (idx, columns) of the last shard
 
-    def take(self, idx):
-        """The sink of the rays ``idx`` (a shard integrated on its own)."""
-        import torch
-        idx = torch.as_tensor(idx, device=self.summary.device).to(torch.int64)
-        return SummarySink(self.summary, idx if self.ray is None else self.ray[idx])
+    ray = property(lambda self: self.per_ray)
 
-    def __call__(self, i0, i1, view, *rest, tails=None, slots=None):
-        import torch
-        idx, tails, slots = _split_call(rest, tails, slots)
-        ray = self.ray
-        if idx is not None:
-            if self._sub[0] is not idx:
-                cols = torch.as_tensor(idx, device=self.summary.device).to(torch.int64)
-                self._sub = (idx, (cols if ray is None else ray[cols]).contiguous())
-            ray = self._sub[1]
-        self.summary.add_rows(i0, i1, view, tails, slots, ray)
+    def select(self, idx):
+        return idx if self.per_ray is None else self.per_ray[idx]
 
 
 class Tee:

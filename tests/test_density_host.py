@@ -255,11 +255,13 @@ def test_density_argument_errors_without_a_gpu():
         (dict(m=m(inv_dlon=INF), wsum=64), b"inv_dlon"), (dict(m=m(inv_dlon=NAN), wsum=64), b"inv_dlon"),
         (dict(m=m(inv_dlat=0.0), wsum=64), b"inv_dlat"), (dict(m=m(inv_dlat=NAN), wsum=64), b"inv_dlat"),
         (dict(m=m(inv_dlat=INF), wsum=64), b"inv_dlat"),
-        (dict(m=good, wsum=64, nray=-1), b"nray"),
+        (dict(m=good, wsum=64, nray=-1), b"nray"), (dict(m=good, wsum=64, nray=1 << 31), b"nray"),
+        (dict(m=good, wsum=64, rows=72), b"16-byte"), (dict(m=good, wsum=64, tfrom=64, trow=72), b"16-byte"),
     ]
     for kw, word in cases:
         assert _call(lib, **kw) == H.RWRT_ERR_ARG, kw
         assert word in lib.rwrt_last_error(), (kw, lib.rwrt_last_error())
+        assert lib.rwrt_last_error().startswith(b"rwrt_ray_density: ")
     # no rays: a no-op (no device is touched; there is none on the build host)
     assert _call(lib, good, nray=0, rows=None, wsum=64) == H.RWRT_OK
     assert _call(lib, m(wcol=-1), nray=0, rows=None, wsum=None) == H.RWRT_OK

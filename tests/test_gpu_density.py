@@ -30,10 +30,12 @@ NRAY, I0, I1 = 130, 1, 8     # three waves, the last partial; 7 rows
 SENTINEL = (1.0, 0.1, 5.0)   # finite, binnable: must never be counted
 
 
-def crafted(seed=0):
+def crafted(seed=0, tf=None):
     """Logical rows ``[130, 7, 8]`` that all three layouts can hold: ray j's
     rows from ``tf[j]`` on repeat its tail row; tf = it_begin / middle / it_end
-    by j % 3 (the j % 3 == 0 rays have no row block in the slots layout)."""
+    by j % 3 (the j % 3 == 0 rays have no row block in the slots layout), or
+    the ``tf`` given, which may lie outside ``[I0, I1]`` (and is at most I0 for
+    those rays)."""
     rng = np.random.default_rng(seed)
     nrow = I1 - I0
     rows = rng.uniform(-3.0, 3.0, (NRAY, nrow, 8))
@@ -49,9 +51,10 @@ def crafted(seed=0):
     tail[:, 1] = rng.uniform(-1.8, 1.8, NRAY)
     tail[5::7, 0] = np.nan                      # frozen NaN rays
     tail[6::11, 4] = np.inf                     # a non-finite weight in a tail
-    tf = np.array([I0, I0 + 3, I1], np.int32)[np.arange(NRAY) % 3]
+    tf = np.array([I0, I0 + 3, I1], np.int32)[np.arange(NRAY) % 3] if tf is None else np.asarray(tf, np.int32)
+    cut = np.clip(tf, I0, I1)
     for j in range(NRAY):
-        rows[j, tf[j] - I0:] = tail[j]
+        rows[j, cut[j] - I0:] = tail[j]
     return rows, tail, tf
 
 
@@ -61,9 +64,10 @@ def layouts(rows, tail, tf, seed=1):
     nrow = I1 - I0
     out = {"dense": (torch.as_tensor(rows, device=DEV).contiguous(), None, None)}
     buf = rows.copy()
+    cut = np.clip(tf, I0, I1)
     for j in range(NRAY):
-        buf[j, tf[j] - I0:] = 0.0
-        buf[j, tf[j] - I0:, 0], buf[j, tf[j] - I0:, 1], buf[j, tf[j] - I0:, 4] = SENTINEL
+        buf[j, cut[j] - I0:] = 0.0
+        buf[j, cut[j] - I0:, 0], buf[j, cut[j] - I0:, 1], buf[j, cut[j] - I0:, 4] = SENTINEL
     t = Tails(NRAY, DEV)
     t.frm.copy_(torch.as_tensor(tf))
     t.row.copy_(torch.as_tensor(tail))
@@ -84,7 +88,25 @@ def layouts(rows, tail, tf, seed=1):
     (DensitySpec(1440, 720, weight="amp"), True), (DensitySpec(1440, 720, nchan=3), True)],
     ids=["7x5", "7x5x3-amp", "1440x720-amp", "1440x720x3"])
 def test_crafted_rows_every_layout(spec, with_chan):
-    rows, tail, tf = crafted()
+    every_layout_equals_reference_bins(spec, with_chan, *crafted())
+
+
+# tail_from below, at and above the launch, and rows read on either side of the kernel's batch of 4
+BOUNDARY_TF = (I0 - 2, I0, I0 + 1, I0 + 3, I0 + 4, I0 + 5, I1, I1 + 3)
+
+
+@pytest.mark.parametrize("spec,with_chan", [(DensitySpec(7, 5, nchan=3, weight="amp"), True)], ids=["7x5x3-amp"])
+def test_crafted_rows_tail_from_clamp_and_batch_boundary(spec, with_chan):
+    """``tail_from`` from BOUNDARY_TF, unclamped, in every layout: 0, 1, 3, 4, 5
+    and 7 rows read (the rays without a row block: at most I0)."""
+    j = np.arange(NRAY)
+    tf = np.where(j % 3 == 0, np.array(BOUNDARY_TF[:2])[(j // 3) % 2], np.array(BOUNDARY_TF)[j % 8])
+    assert all(set(tf[j % 3 == r].tolist()) == set(BOUNDARY_TF) for r in (1, 2))
+    assert sorted(set((np.clip(tf, I0, I1) - I0).tolist())) == [0, 1, 3, 4, 5, 7]
+    every_layout_equals_reference_bins(spec, with_chan, *crafted(seed=4, tf=tf))
+
+
+def every_layout_equals_reference_bins(spec, with_chan, rows, tail, tf):
     rng = np.random.default_rng(7)
     chan = rng.integers(-1, spec.nchan + 1, NRAY).astype(np.int32) if with_chan else None
     cref = None if chan is None else chan[:, None]

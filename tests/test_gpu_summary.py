@@ -62,17 +62,19 @@ NCOL = 200                   # the accumulators are wider than the ray set
 SENTINEL = (0.1, 1.55, -9.0, 1e6)   # lon lat l amp: valid, inside boxes, beyond every real lat and amp
 
 
-def crafted(seed=0):
+def crafted(seed=0, frz=None):
     """Logical rows ``[130, 8, 8]`` and each ray's freeze row ``frz`` (rows from
     ``frz`` on repeat row ``frz``; 8: never): frozen from row 1 on (j % 3 == 0,
-    no row block in the slots layout), from a row in 2..6, or live; NaN tails,
-    NaN first rows and NaN holes on either side of the split at row 4."""
+    no row block in the slots layout), from a row in 2..6, or live -- or the
+    ``frz`` given; NaN tails, NaN first rows and NaN holes on either side of
+    the split at row 4."""
     rng = np.random.default_rng(seed)
     rows = rng.uniform(-3.0, 3.0, (NRAY, NROW, 8))
     rows[..., 0] = rng.uniform(-70.0, 70.0, (NRAY, NROW))
     rows[..., 1] = rng.uniform(-1.5, 1.5, (NRAY, NROW))
     j = np.arange(NRAY)
-    frz = np.where(j % 3 == 0, 1, np.where(j % 3 == 1, 2 + j % 5, NROW))
+    if frz is None:
+        frz = np.where(j % 3 == 0, 1, np.where(j % 3 == 1, 2 + j % 5, NROW))
     rows[j % 13 == 5, 0] = NAN                     # no initial row
     rows[0, 0] = NAN                               # (ray 0 is NaN from row 1 on too: no valid row at all)
     rows[(j % 3 == 2) & (j % 5 == 2), 3, :2] = NAN   # a hole before the split ...
@@ -87,9 +89,10 @@ def crafted(seed=0):
     return rows, frz
 
 
-def layouts(rows, frz, i0, i1, seed=1):
+def layouts(rows, frz, i0, i1, seed=1, frm=None):
     """``name -> (view, tails, slots)`` device objects of the logical rows
-    ``[i0, i1)``; what a launch would not write holds SENTINEL."""
+    ``[i0, i1)``; what a launch would not write holds SENTINEL.  ``frm``: the
+    ``tail_from`` handed over (default: ``frz`` clipped to the launch)."""
     rng = np.random.default_rng(seed + i0)
     out = {"dense": (torch.as_tensor(rows[:, i0:i1], device=DEV).contiguous(), None, None)}
     tf = np.clip(frz, i0, i1).astype(np.int32)
@@ -99,7 +102,7 @@ def layouts(rows, frz, i0, i1, seed=1):
         for c, v in zip((0, 1, 3, 4), SENTINEL):
             buf[j, tf[j] - i0:, c] = v
     t = Tails(NRAY, DEV)
-    t.frm.copy_(torch.as_tensor(tf))
+    t.frm.copy_(torch.as_tensor(tf if frm is None else np.asarray(frm, np.int32)))
     tail = rows[np.arange(NRAY), np.minimum(tf, i1 - 1)].copy()
     tail[tf >= i1] = [SENTINEL[0], SENTINEL[1], 0.0, SENTINEL[2], SENTINEL[3], 0.0, 0.0, 0.0]   # (no tail: unread)
     t.row.copy_(torch.as_tensor(tail))
@@ -121,6 +124,24 @@ def test_crafted_rows_every_layout(nreg):
     columns: rows 1..7 in one call and split at row 4 (the carried previous
     row), dense, with tails and with row blocks."""
     rows, frz = crafted()
+    every_layout_equals_reference_summary(rows, frz, nreg, ([(1, 8)], [(1, 4), (4, 8)]))
+
+
+@pytest.mark.parametrize("nreg", [0, 1, 8])
+def test_crafted_rows_tail_from_clamp_and_batch_boundary(nreg):
+    """Rows 1..7 in one call with ``tail_from`` below, at and above the launch,
+    handed over unclamped, and 0, 1, 3, 4, 5 and 7 rows read: on either side
+    of the kernel's batch of 4."""
+    i0, i1 = 1, NROW
+    j = np.arange(NRAY)
+    frm = np.array([i0 - 2, i0, i0 + 1, i0 + 3, i0 + 4, i0 + 5, i1, i1 + 3])[j % 8]
+    frz = np.clip(frm, i0, i1)
+    assert sorted(set((frz - i0).tolist())) == [0, 1, 3, 4, 5, 7]
+    rows, frz = crafted(seed=4, frz=frz)
+    every_layout_equals_reference_summary(rows, frz, nreg, ([(i0, i1)],), frm)
+
+
+def every_layout_equals_reference_summary(rows, frz, nreg, all_splits, frm=None):
     regions = REGIONS8[:nreg]
     want = reference_summary(rows, regions)
     non_vacuous(want, nreg)
@@ -128,13 +149,13 @@ def test_crafted_rows_every_layout(nreg):
     cols = np.random.default_rng(3).permutation(NCOL)[:NRAY]
     ray = torch.as_tensor(cols, device=DEV)
     spare = np.setdiff1d(np.arange(NCOL), cols)
-    for splits in ([(1, 8)], [(1, 4), (4, 8)]):
+    for splits in all_splits:
         for name in ("dense", "tails", "slots"):
             rs = RaySummary(NCOL, regions, DEV)
             fresh = rs.numpy()
             rs.start(rows[:, 0, 0], rows[:, 0, 1], rows[:, 0, 3], rows[:, 0, 4], ray=ray)
             for i0, i1 in splits:
-                view, tails, slots = layouts(rows, frz, i0, i1)[name]
+                view, tails, slots = layouts(rows, frz, i0, i1, frm=frm)[name]
                 rs.add_rows(i0, i1, view, tails, slots, ray)
             got = check(rs, want, (nreg, splits, name), cols)
             full = rs.numpy()

@@ -326,6 +326,7 @@ def test_summary_argument_errors_without_a_gpu():
     for kw, word in cases:
         assert _call(lib, **kw) == H.RWRT_ERR_ARG, kw
         assert word in lib.rwrt_last_error(), (kw, lib.rwrt_last_error())
+        assert lib.rwrt_last_error().startswith(b"rwrt_ray_summary: ")
     # no rays: a no-op (no device is touched; there is none on the build host)
     assert _call(lib, nray=0, rows=None) == H.RWRT_OK
     assert _call(lib, nray=0, rows=None, reg=reg(8), ncol=0) == H.RWRT_OK
