@@ -39,7 +39,8 @@ extern "C" {
                                   per-ray path summaries (rwrt_ray_summary) and the wavenumber
                                   map (rwrt_wn_map, rwrt_wn_fill) joined ABI 5 later as additive
                                   members, and so did the spherical-harmonic filter
-                                  (rwrt_sh_filter): no earlier signature or layout changed */
+                                  (rwrt_sh_filter) and the arrival-time maps
+                                  (rwrt_ray_arrival): no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -448,6 +449,37 @@ rwrt_status rwrt_ray_summary(int64_t nray, int32_t it_begin, int32_t it_end,
                              const int64_t* d_ray, int64_t nacc_cols,
                              const rwrt_summary_regions* reg,
                              double* d_f64, int32_t* d_i32, void* stream);
+
+/* ABI 5, additive: arrival-time maps.  The same rows reduced per map box to
+ * WHEN ray points fall into it: the first and the last output row with a point
+ * in the box and, per time window of window_rows rows, how many points.  The
+ * definition is arrival.reference_arrival (NumPy); csrc/arrival_rows.h
+ * restates it and every output equals NumPy's exactly.  A point is binned as
+ * by rwrt_ray_density (`bins`), with bins.wcol read as "the row column that
+ * must be finite" (-1: none): nothing is summed.  Row i lies in window
+ * i / window_rows. */
+typedef struct {
+  rwrt_density_map bins;
+  int32_t window_rows;           /* 0: no counts (d_count is not used) */
+  int32_t nwin;                  /* windows of d_count; it_end <= nwin * window_rows */
+} rwrt_arrival_map;              /* 48 bytes */
+
+/* Reduces rows it_begin <= i < it_end of nray rays and ACCUMULATES into
+ * d_first[nchan][ny][nx] (int32, min of the row index), d_last (int32, max)
+ * and, with window_rows > 0, d_count[nwin][nchan][ny][nx] (int64, add;
+ * nwin*nchan*ny*nx < 2^31): the caller writes INT32_MAX, -1 and 0 once, so
+ * time chunks and shards combine.  Row layouts, d_chan and their argument
+ * rules are those of rwrt_ray_density.  Equal-bin runs of a ray's consecutive
+ * rows are combined before the atomics (one min, one max, one add per run and
+ * one more add per window the run enters); a constant tail is one run and
+ * costs one add per window it touches.  Asynchronous and ordered on `stream`;
+ * needs no rwrt_ctx.  nray == 0 is a no-op. */
+rwrt_status rwrt_ray_arrival(const rwrt_arrival_map* m, int64_t nray,
+                             int32_t it_begin, int32_t it_end,
+                             const double* d_rows, const int32_t* d_row_slot,
+                             const int32_t* d_tail_from, const double* d_tail_row,
+                             const int32_t* d_chan, int32_t* d_first, int32_t* d_last,
+                             int64_t* d_count, void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

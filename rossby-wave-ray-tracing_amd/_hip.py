@@ -20,7 +20,8 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_mercator_point", "rwrt_rhs", "rwrt_dp54_attempt",
                "rwrt_ray_initial", "rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails",
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
-               "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_wn_map", "rwrt_wn_fill",
+               "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival",
+               "rwrt_wn_map", "rwrt_wn_fill",
                "rwrt_sh_filter",
                "rwrt_bs_ready", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
                "rwrt_rk45_run_tv_slots", "rwrt_rhs_tv",
@@ -62,6 +63,12 @@ class DensityMap(ctypes.Structure):
                 ("lat0", ctypes.c_double), ("inv_dlat", ctypes.c_double)]
 
 
+class ArrivalMap(ctypes.Structure):
+    """``rwrt_arrival_map``: the map a ``rwrt_ray_arrival`` call reduces into
+    (``bins.wcol``: the row column that must be finite)."""
+    _fields_ = [("bins", DensityMap), ("window_rows", ctypes.c_int32), ("nwin", ctypes.c_int32)]
+
+
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
 
 
@@ -93,6 +100,7 @@ def load():
     G, Pr, B = ctypes.POINTER(Grid), ctypes.POINTER(Params), ctypes.POINTER(Background)
     M = ctypes.POINTER(DensityMap)
     R = ctypes.POINTER(SummaryRegions)
+    A = ctypes.POINTER(ArrivalMap)
     sig = {
         "rwrt_pack_fields": [G, _P, _P, _P],
         "rwrt_mercator_point": [G, _P, _I64, _P, _P, _P, _P],
@@ -110,6 +118,7 @@ def load():
         "rwrt_expand_slots": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P],
         "rwrt_rk4_run": [_P, G, _P, _I64, Pr, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_density": [M, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
+        "rwrt_ray_arrival": [A, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_summary": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, R, _P, _P, _P],
         "rwrt_wn_map": [G, _P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_wn_fill": [_I32, _I32, _I32, _I32, _P, _P, _P],

@@ -286,6 +286,57 @@ class WR:
             dmap.allreduce(group)
         return dmap
 
+    def ray_arrival(self, spec, mode="hip", inte_method="rk45", by=None, include_initial=True,
+                    group=None, root_method="numpy"):
+        """Initialise and integrate all rays like ``ray_run``, but reduce every
+        output row into an arrival-time map on the GPU (arrival.py) instead of
+        delivering the history: returns the ``arrival.ArrivalMap`` -- per map
+        box the first and the last row with a ray point in it and, per time
+        window, how many; only row 0 of ``rlon .. rvg`` is filled.
+
+        ``spec``: an ``arrival.ArrivalSpec`` whose ``nt`` equals this run's.
+        ``by``, ``include_initial``: as in ``ray_density``.  ``mode='numpy'``
+        integrates on the GPU all the same, delivers the history and applies
+        ``arrival.reference_arrival`` on the host (small runs; returns its
+        dict).  With a process ``group`` every rank ends with the reduced map."""
+        import arrival as A
+        import density as D
+        if by not in (None, "zwn", "root"):
+            raise ValueError("by must be None, 'zwn' or 'root'")
+        if spec.nt != self.nt:
+            raise ValueError(f"spec.nt is {spec.nt}, the run has {self.nt} rows")
+        shape = (3, self.nsource, self.nzwn)
+        nray = 3 * self.nsource * self.nzwn
+        chan = None
+        if by is not None:
+            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
+            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
+            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
+        col = spec.bins.wcol
+
+        def required(rows):
+            return None if col < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[col - 2][rows]
+
+        if mode == "numpy":
+            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
+            first = 0 if include_initial else 1
+            pts = [None if a is None else a.reshape(-1, nray).T
+                   for a in (self.rlon[first:], self.rlat[first:], required(slice(first, None)))]
+            return A.reference_arrival(pts[0], pts[1], pts[2], chan, spec, row0=first)
+        key = mode + "_rk45" if inte_method == "rk45" else mode
+        if key not in SUPPORTED:
+            self.core_ray_run(key)     # raises before any work
+        self.ray_initial(mode=mode, root_method=root_method)
+        import shard
+        rank, world = shard.world_info(group) if group is not None else (0, 1)
+        amap = A.ArrivalMap(spec, self.bs.engine().device)
+        if include_initial and rank == 0:
+            amap.add_points(self.rlon[0], self.rlat[0], required(0), chan)
+        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=A.ArrivalSink(amap, chan))
+        if group is not None and shard.collective(world):
+            amap.allreduce(group)
+        return amap
+
     def ray_summary(self, regions=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but reduce every
         ray's rows to a path summary on the GPU (summary.py) instead of
