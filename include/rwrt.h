@@ -39,8 +39,9 @@ extern "C" {
                                   per-ray path summaries (rwrt_ray_summary) and the wavenumber
                                   map (rwrt_wn_map, rwrt_wn_fill) joined ABI 5 later as additive
                                   members, and so did the spherical-harmonic filter
-                                  (rwrt_sh_filter) and the arrival-time maps
-                                  (rwrt_ray_arrival): no earlier signature or layout changed */
+                                  (rwrt_sh_filter), the arrival-time maps
+                                  (rwrt_ray_arrival) and the basic-state diagnostics
+                                  (rwrt_bs_diag): no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -512,6 +513,43 @@ rwrt_status rwrt_bs_ready(int32_t nlon, int32_t nlat, const float* d_u,
                           const float* d_v, const double* d_trig, double dx,
                           double dy, double* d_scratch, void* d_packed,
                           int32_t fp32, void* stream);
+
+/* The basic-state diagnostics (ABI 5, additive): the 23 fields that BS.output
+ * writes (bs.py:461-511) after BS.ready(xcyclic=True) (bs.py:318-407), for a
+ * batch of nlev levels.  Plane ids, in BS.output's order (bs.py:481-505):
+ *   0 u  1 v  2 q  3 ux  4 uxx  5 uy  6 vx  7 vxx  8 vy  9 qx  10 qy  11 qxx
+ *   12 qxy  13 qyx  14 qyy  15 qxxx  16 qxxy  17 qxyy  18 qyyy  19 qyxx
+ *   20 qyyx  21 betam  22 KS
+ * Plane p of a level is bit for bit (NaN for NaN) the attribute of that name:
+ * qxx, qxy, qyy after smth9, qyx the copy taken before it, the third
+ * derivatives from the unsmoothed second derivatives.  On rows 1..nlat-2
+ *   betam = ((2 Omega)(c c) + (((-c) uyy + s uy) + u / c) / R) / R
+ *   KS    = sqrt((betam c) / u) R   where betam > 0 and u > 0, NaN elsewhere
+ * with c, s = d_trig[1], d_trig[2], u the float32 value widened and uyy =
+ * gradient_yy(u); rows 0 and nlat-1 of both are NaN.  Every operation is
+ * + - * / sqrt in fp64 in NumPy's evaluation order.
+ *  d_u, d_v [nlev][nlat][nlon] float32, file layout, ascending latitude;
+ *    d_trig, dx, dy exactly rwrt_bs_ready's.
+ *  select: bit p set = plane p is written.  d_out
+ *    [nlev][popcount(select)][nlon][nlat], the selected planes in ascending id.
+ *  d_scratch: needed only when select has a plane derived from q (ids 2,
+ *    9..20): 4*nlon*nlat*scratch_levels doubles (rwrt_bs_ready's q, qxx, qyy,
+ *    qxy of every level in flight); the call then works through the levels in
+ *    groups of scratch_levels, one set of launches per group.  Without such a
+ *    plane d_scratch may be NULL, scratch_levels is ignored and the call is one
+ *    launch.  Results depend neither on scratch_levels nor on the batch a level
+ *    is in; no atomics.
+ * RWRT_ERR_ARG before any HIP call: nlon < 3, nlat < 4, nlev < 0, select == 0
+ * or with bits >= RWRT_NDIAG, a NULL d_u, d_v, d_trig or d_out, scratch needed
+ * but NULL or scratch_levels < 1, d_out (or the scratch) overlapping an input.
+ * nlev == 0 is a no-op.  Asynchronous, ordered on stream; needs no rwrt_ctx. */
+#define RWRT_NDIAG 23
+rwrt_status rwrt_bs_diag(int32_t nlon, int32_t nlat, int32_t nlev,
+                         const float* d_u, const float* d_v,
+                         const double* d_trig, double dx, double dy,
+                         uint32_t select, double* d_out, double* d_scratch,
+                         int32_t scratch_levels, void* stream);
+
 /* rwrt_rk45_init / rwrt_rk45_run on a time-varying background (same state,
  * queue and output conventions).  Steps reuse K6 = fun(t + h, y_new) as the
  * next f (FSAL, scipy's RK45 convention); the per-row group velocity is

@@ -23,7 +23,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival",
                "rwrt_wn_map", "rwrt_wn_fill",
                "rwrt_sh_filter",
-               "rwrt_bs_ready", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
+               "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
                "rwrt_rk45_run_tv_slots", "rwrt_rhs_tv",
                "rwrt_kat_rk45", "rwrt_selftest_math", "rwrt_host_fill_rows")
 
@@ -70,6 +70,7 @@ class ArrivalMap(ctypes.Structure):
 
 
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
+NDIAG = 23     # RWRT_NDIAG: the planes of rwrt_bs_diag
 
 
 class SummaryRegions(ctypes.Structure):
@@ -124,6 +125,7 @@ def load():
         "rwrt_wn_fill": [_I32, _I32, _I32, _I32, _P, _P, _P],
         "rwrt_sh_filter": [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_bs_ready": [_I32, _I32, _P, _P, _P, _D, _D, _P, _P, _I32, _P],
+        "rwrt_bs_diag": [_I32, _I32, _I32, _P, _P, _P, _D, _D, ctypes.c_uint32, _P, _P, _I32, _P],
         "rwrt_rk45_init_tv": [G, B, _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
         "rwrt_rk45_run_tv": [_P, G, B, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],
         "rwrt_rk45_run_tv_tails": [_P, G, B, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P,

@@ -205,6 +205,16 @@ class BS:
             vars_[n] = (("lon", "lat"), np.asarray(getattr(self, n), dtype=self.all_dtype_))
         ncio.write(ncfile, {"lon": self.nlon, "lat": self.nlat}, vars_)
 
+    def diagnostics(self, names=None, device=None):
+        """The fields ``output`` writes (``bsdiag.DIAG_NAMES``; default all 23),
+        computed on the GPU from this state's own ``u, v`` and axes
+        (``bsdiag.BSDiag``): a device tensor ``[len(names), nlon, nlat]``, each
+        plane bit-identical to the attribute of that name after
+        ``ready(xcyclic=True)``.  ``ready`` need not have been called."""
+        from bsdiag import BSDiag
+        d = BSDiag.from_axes(self.lat, self.lon, self.dx[0], self.dy[0], device)
+        return d.compute(np.ascontiguousarray(self.u.T), np.ascontiguousarray(self.v.T), names)[0]
+
     def clean(self):
         for k in ["u", "v", "q", "fields", "betam", "KS"] + FIELD_NAMES[2:]:
             if hasattr(self, k):

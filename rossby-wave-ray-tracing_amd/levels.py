@@ -51,7 +51,7 @@ class Levels:
         if not (lat_deg[0] < lat_deg[-1]):
             raise ValueError("Levels needs an ascending latitude axis (flip u, v, lat first)")
         self.nlat, self.nlon = len(lat_deg), len(lon_deg)
-        self.lat_deg, self._filters = lat_deg, {}
+        self.lat_deg, self._filters, self._diag = lat_deg, {}, None
         # the axes exactly as BS.loadbs_ncfile builds them (float32 arithmetic)
         b = BS(self.nlon, self.nlat)
         b.load_arrays(np.zeros((self.nlat, self.nlon), np.float32),
@@ -119,6 +119,17 @@ class Levels:
             shsf.check_grid(self.nlat, self.nlon, self.lat_deg)
             self._filters[trunc] = shsf.SHFilter(self.nlat, self.nlon, trunc, self.device)
         return self._filters[trunc]
+
+    def diagnostics(self, u, v, names=("betam", "KS"), trunc=None):
+        """Basic-state diagnostics of ``u, v[nlev, nlat, nlon]`` (or one
+        ``[nlat, nlon]`` level; any number of levels, not only ``self.nlev``) on
+        this stack's axes and device: a device tensor ``[nlev, len(names), nlon,
+        nlat]`` (``bsdiag.BSDiag.compute``; the names are ``bsdiag.DIAG_NAMES``).
+        The stack itself keeps no ``u, v``, so they are passed in."""
+        if self._diag is None:
+            from bsdiag import BSDiag
+            self._diag = BSDiag.from_axes(self.lat, self.lon, self.dx, self.dy, self.device, self.lat_deg)
+        return self._diag.compute(u, v, names, trunc=trunc)
 
     def background(self):
         """The ``rwrt_background`` description of these levels."""

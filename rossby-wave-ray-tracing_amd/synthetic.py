@@ -17,13 +17,20 @@ them from netCDF: ``u, v`` float32 ``(nlat, nlon)``, ``lat, lon`` float32.
 """
 import numpy as np
 
-__all__ = ["background", "background_level", "SeedConfig", "CONFIGS", "config"]
+__all__ = ["background", "background_on", "background_level", "SeedConfig", "CONFIGS", "config"]
 
 
 def background(kind="zonal", res=2.5):
     """Return ``dict(u, v, lat, lon)`` for a deterministic synthetic basic state."""
     lat = np.arange(-90.0, 90.0 + res / 2, res).astype(np.float32)
     lon = np.arange(0.0, 360.0, res).astype(np.float32)
+    return background_on(kind, lat, lon)
+
+
+def background_on(kind, lat, lon):
+    """``background`` evaluated on given degree axes (any ``nlat``, ``nlon``)."""
+    lat = np.asarray(lat, np.float32)
+    lon = np.asarray(lon, np.float32)
     phi = lat.astype(np.float64)[:, None]
     lam = lon.astype(np.float64)[None, :]
     jets = (45.0 * np.exp(-((phi - 32.0) / 10.0) ** 2)
