@@ -40,8 +40,9 @@ extern "C" {
                                   map (rwrt_wn_map, rwrt_wn_fill) joined ABI 5 later as additive
                                   members, and so did the spherical-harmonic filter
                                   (rwrt_sh_filter), the arrival-time maps
-                                  (rwrt_ray_arrival) and the basic-state diagnostics
-                                  (rwrt_bs_diag): no earlier signature or layout changed */
+                                  (rwrt_ray_arrival), the basic-state diagnostics
+                                  (rwrt_bs_diag) and the wave-ray flux maps
+                                  (rwrt_ray_flux): no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -481,6 +482,58 @@ rwrt_status rwrt_ray_arrival(const rwrt_arrival_map* m, int64_t nray,
                              const int32_t* d_tail_from, const double* d_tail_row,
                              const int32_t* d_chan, int32_t* d_first, int32_t* d_last,
                              int64_t* d_count, void* stream);
+
+/* ABI 5, additive: wave-ray flux maps.  The same rows reduced per map box to
+ * a vector: the sum of the group velocities (or of their directions) of the
+ * ray points in the box, with their number, the sum of their row indices and
+ * the sum of their speeds -- the magnitude and direction of wave activity, the
+ * mean propagation time and the mean speed per box.  The definition is
+ * flux.reference_flux (NumPy); csrc/flux_rows.h restates it.
+ *
+ * A row (lon lat k l amp ug vg) at row index i of a ray with channel c is
+ * accepted iff 0 <= c < nchan; lon, lat, ug, vg are finite; |k| <= wn_max and
+ * |l| <= wn_max (false for NaN); s2 = ug*ug + vg*vg (two rounded products, one
+ * rounded sum, no FMA) is finite and s2_min <= s2 <= s2_max; with unit vectors
+ * s2 > 0; and the point falls in a bin.  The latitude index is
+ * rwrt_ray_density's.  The longitude index is rwrt_ray_density's too (wrapped,
+ * nx bins over [0, 2 pi), lon0 = 0), or, with mode bit 1, that of the
+ * UNWRAPPED window: fx = floor((lon - lon0) * inv_dlon), binned iff
+ * 0 <= fx < nx compared in fp64 -- the ray loops never wrap lon, so eastward
+ * and westward routes around the globe stay apart.  With speed = sqrt(s2) an
+ * accepted point adds 1 and i to the bin's integers and (ug, vg, speed) -- with
+ * mode bit 0 (ug / speed, vg / speed, speed) -- to its sums.  The amplitude is
+ * no criterion. */
+typedef struct {
+  int32_t nx, ny, nchan;
+  int32_t mode;             /* bit 0: unit vectors; bit 1: unwrapped longitude window */
+  double lon0, inv_dlon;    /* rad; nx / (lon1 - lon0).  wrapped: 0 and nx / (2 pi) */
+  double lat0, inv_dlat;    /* rad; ny / (lat1 - lat0) */
+  double s2_min, s2_max;    /* squares of the speed bounds, computed once by the caller */
+  double wn_max;
+} rwrt_flux_map;            /* 72 bytes */
+
+/* Reduces rows it_begin <= i < it_end of nray rays and ACCUMULATES into
+ * d_cnt[nchan][ny][nx][2] (int64: count, rowsum) and d_sum[nchan][ny][nx][3]
+ * (fp64: fx, fy, fs): the caller zeroes them once, so time chunks and shards
+ * add up.  A bin's accumulators are interleaved so that one update touches
+ * neighbouring addresses.  Row layouts, d_chan and their argument rules are
+ * those of rwrt_ray_density.  Equal-bin runs of a ray's consecutive rows are
+ * summed in row order before the atomics (two integer and three fp64 adds per
+ * run); a constant tail of n rows from row tf on is one run: count += n,
+ * rowsum += n tf + n (n - 1) / 2, each sum += v * n.  count and rowsum are
+ * exact; the sums depend on the arrival order in their last bits.
+ * RWRT_ERR_ARG before any HIP call: a NULL map, d_cnt or d_sum; nx, ny or
+ * nchan not positive; nchan*ny*nx >= 2^31; mode bits >= 4; inv_dlon or
+ * inv_dlat not finite and positive; lon0 or lat0 not finite; wrapped with
+ * lon0 != 0; s2_min NaN or negative, s2_max NaN or below s2_min; wn_max NaN or
+ * negative; the row arguments as for rwrt_ray_density.  Asynchronous and
+ * ordered on `stream`; needs no rwrt_ctx.  nray == 0 is a no-op. */
+rwrt_status rwrt_ray_flux(const rwrt_flux_map* m, int64_t nray,
+                          int32_t it_begin, int32_t it_end,
+                          const double* d_rows, const int32_t* d_row_slot,
+                          const int32_t* d_tail_from, const double* d_tail_row,
+                          const int32_t* d_chan, int64_t* d_cnt, double* d_sum,
+                          void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

@@ -20,7 +20,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_mercator_point", "rwrt_rhs", "rwrt_dp54_attempt",
                "rwrt_ray_initial", "rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails",
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
-               "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival",
+               "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival", "rwrt_ray_flux",
                "rwrt_wn_map", "rwrt_wn_fill",
                "rwrt_sh_filter",
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
@@ -69,6 +69,17 @@ class ArrivalMap(ctypes.Structure):
     _fields_ = [("bins", DensityMap), ("window_rows", ctypes.c_int32), ("nwin", ctypes.c_int32)]
 
 
+class FluxMapC(ctypes.Structure):
+    """``rwrt_flux_map``: the map a ``rwrt_ray_flux`` call reduces into (``mode``
+    bit 0: unit vectors, bit 1: unwrapped longitude window)."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nchan", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("lon0", ctypes.c_double), ("inv_dlon", ctypes.c_double),
+                ("lat0", ctypes.c_double), ("inv_dlat", ctypes.c_double),
+                ("s2_min", ctypes.c_double), ("s2_max", ctypes.c_double), ("wn_max", ctypes.c_double)]
+
+
+assert ctypes.sizeof(FluxMapC) == 72
+
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
 NDIAG = 23     # RWRT_NDIAG: the planes of rwrt_bs_diag
 
@@ -102,6 +113,7 @@ def load():
     M = ctypes.POINTER(DensityMap)
     R = ctypes.POINTER(SummaryRegions)
     A = ctypes.POINTER(ArrivalMap)
+    F = ctypes.POINTER(FluxMapC)
     sig = {
         "rwrt_pack_fields": [G, _P, _P, _P],
         "rwrt_mercator_point": [G, _P, _I64, _P, _P, _P, _P],
@@ -120,6 +132,7 @@ def load():
         "rwrt_rk4_run": [_P, G, _P, _I64, Pr, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_density": [M, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_arrival": [A, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+        "rwrt_ray_flux": [F, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_summary": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, R, _P, _P, _P],
         "rwrt_wn_map": [G, _P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_wn_fill": [_I32, _I32, _I32, _I32, _P, _P, _P],

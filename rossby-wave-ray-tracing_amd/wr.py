@@ -337,6 +337,86 @@ class WR:
             amap.allreduce(group)
         return amap
 
+    def ray_flux(self, spec, mode="hip", inte_method="rk45", by=None, through=None, through_mode="any",
+                 include_initial=True, group=None, root_method="numpy"):
+        """Initialise and integrate all rays like ``ray_run``, but reduce every
+        output row into a wave-ray flux map on the GPU (flux.py) instead of
+        delivering the history: returns the ``flux.FluxMap`` -- per map box
+        the summed group-velocity (or unit) vectors of the accepted ray points,
+        their number, the sum of their rows and of their speeds; only row 0 of
+        ``rlon .. rvg`` is filled.
+
+        ``spec``: a ``flux.FluxSpec``.  ``by``, ``include_initial``: as in
+        ``ray_density``.  ``through``: up to 8 boxes ``(lon_w, lon_e, lat_s,
+        lat_n)`` in degrees (the regions of ``ray_summary``); only the rays
+        that pass through any (``through_mode='any'``) or every (``'all'``) box
+        contribute.  That costs a second integration: the first one reduces
+        the rays to a ``ray_summary`` with these regions, the rays that do not
+        pass get channel -1, the second one reduces the flux (the initial rows
+        are deterministic: both see the same rays).  The map's ``selected`` is
+        then a bool array ``(3, nsource, nzwn)``, else None.  ``mode='numpy'``
+        integrates on the GPU all the same, delivers the history and applies
+        ``flux.reference_flux`` (and ``summary.reference_summary`` for the
+        selection) on the host (small runs; returns the dict of
+        ``reference_flux`` with ``'selected'`` added).  With a process
+        ``group`` every rank ends with the sum over the ranks."""
+        import density as D
+        import flux as F
+        if by not in (None, "zwn", "root"):
+            raise ValueError("by must be None, 'zwn' or 'root'")
+        if through_mode not in ("any", "all"):
+            raise ValueError("through_mode must be 'any' or 'all'")
+        if through is not None and not 1 <= len(through) <= 8:
+            raise ValueError("through must be None or 1 to 8 boxes (lon_w, lon_e, lat_s, lat_n)")
+        shape = (3, self.nsource, self.nzwn)
+        nray = 3 * self.nsource * self.nzwn
+        chan = None
+        if by is not None:
+            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
+            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
+            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
+
+        def only(selected):      # channel -1 for the rays that do not pass
+            return np.where(selected, 0 if chan is None else chan, -1).astype(np.int32)
+
+        if mode == "numpy":
+            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
+            hist = (self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)
+            selected = None
+            if through is not None:
+                import summary as Sm
+                rows = np.full((nray, self.nt, 8), np.nan)
+                for c, h in enumerate(hist):
+                    rows[:, :, c] = h.reshape(self.nt, nray).T
+                first_row = Sm.reference_summary(rows, through)["first_row"] >= 0
+                selected = first_row.any(axis=0) if through_mode == "any" else first_row.all(axis=0)
+                chan = only(selected)
+            first = 0 if include_initial else 1
+            pts = [hist[c][first:].reshape(-1, nray).T for c in (0, 1, 2, 3, 5, 6)]
+            out = F.reference_flux(*pts, chan, spec, row0=first)
+            out["selected"] = None if selected is None else selected.reshape(shape)
+            return out
+        key = mode + "_rk45" if inte_method == "rk45" else mode
+        if key not in SUPPORTED:
+            self.core_ray_run(key)     # raises before any work
+        selected = None
+        if through is not None:
+            rs = self.ray_summary(regions=through, mode=mode, inte_method=inte_method, group=group,
+                                  root_method=root_method)
+            selected = F.select_through(rs, through_mode).cpu().numpy()
+            chan = only(selected)
+        self.ray_initial(mode=mode, root_method=root_method)
+        import shard
+        rank, world = shard.world_info(group) if group is not None else (0, 1)
+        fmap = F.FluxMap(spec, self.bs.engine().device)
+        fmap.selected = None if selected is None else selected.reshape(shape)
+        if include_initial and rank == 0:
+            fmap.add_points(self.rlon[0], self.rlat[0], self.rzwn[0], self.rmwn[0], self.rug[0], self.rvg[0], chan)
+        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=F.FluxSink(fmap, chan))
+        if group is not None and shard.collective(world):
+            fmap.allreduce(group)
+        return fmap
+
     def ray_summary(self, regions=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but reduce every
         ray's rows to a path summary on the GPU (summary.py) instead of
