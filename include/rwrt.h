@@ -41,8 +41,10 @@ extern "C" {
                                   members, and so did the spherical-harmonic filter
                                   (rwrt_sh_filter), the arrival-time maps
                                   (rwrt_ray_arrival), the basic-state diagnostics
-                                  (rwrt_bs_diag) and the wave-ray flux maps
-                                  (rwrt_ray_flux): no earlier signature or layout changed */
+                                  (rwrt_bs_diag), the wave-ray flux maps
+                                  (rwrt_ray_flux) and the residence-time maps along ray
+                                  segments (rwrt_ray_track): no earlier signature or layout
+                                  changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -534,6 +536,85 @@ rwrt_status rwrt_ray_flux(const rwrt_flux_map* m, int64_t nray,
                           const int32_t* d_tail_from, const double* d_tail_row,
                           const int32_t* d_chan, int64_t* d_cnt, double* d_sum,
                           void* stream);
+
+/* ABI 5, additive: residence-time maps along ray segments.  The point maps
+ * above bin one point per ray per row; here the straight segment (in lon-lat)
+ * between two consecutive valid rows of a ray is deposited into every map box
+ * it passes through, each box receiving the fraction of the segment inside it,
+ * so that a map does not depend on the output interval, has no gaps and
+ * conserves the total: every live segment deposits exactly one row interval.
+ * The definition is track.reference_track (Python); csrc/track_cells.h
+ * restates it.
+ *
+ * Grid coordinates of a row: X = (lon - lon0) * inv_dlon and
+ * Y = (lat - lat0) * inv_dlat (one rounded subtraction, one rounded product,
+ * no FMA); lon is never wrapped (wrapped maps have lon0 = 0), so X may be
+ * negative or above nx.  A row is valid iff lon and lat are finite and, when
+ * need >= 0 / wcol >= 0, its columns `need` / `wcol` are finite.  Segment i
+ * joins rows i-1 and i of a ray and is considered iff both are valid and the
+ * ray's channel is in [0, nchan).  With fx0 fy0 fx1 fy1 the floors of its end
+ * points (fp64) it is DROPPED -- d_dropped += 1 and nothing else -- if any
+ * |f| > 2^30 or ncx + ncy + 1 > max_cells, ncx = |fx1 - fx0|, ncy =
+ * |fy1 - fy0|, both compared in fp64 before any conversion.  Otherwise it
+ * starts in cell (fx0, fy0) at t = 0 and crosses ncx x-lines and ncy y-lines,
+ * line g at t = (g - X0) / (X1 - X0) resp. (g - Y0) / (Y1 - Y0) (IEEE
+ * division), taken in ascending t, a tie going to x; the cell left at t_next
+ * is emitted with weight t_next - t, the last cell with 1.0 - t, a segment
+ * inside one cell with exactly 1.0.  An emitted cell (ix, iy, w) is deposited
+ * iff 0 <= iy < ny and, wrapped, into column ix mod nx (non-negative) or, with
+ * mode bit 1 (the unwrapped window of rwrt_flux_map), iff 0 <= ix < nx:
+ * cnt += 1, time += w and, with wcol >= 0, wsum += w * (0.5 * (v0 + v1)), v
+ * the column wcol at the two ends. */
+typedef struct {
+  int32_t nx, ny, nchan;
+  int32_t mode;             /* bit 1: unwrapped longitude window; no other bit */
+  int32_t need, wcol;       /* row columns, -1 (none) or 2..6: must be finite / is integrated */
+  int32_t max_cells;        /* >= 1: the most cells one segment may pass through */
+  int32_t reserved;
+  double lon0, inv_dlon;    /* rad; nx / (lon1 - lon0).  wrapped: 0 and nx / (2 pi) */
+  double lat0, inv_dlat;    /* rad; ny / (lat1 - lat0) */
+} rwrt_track_map;           /* 64 bytes */
+
+/* Deposits the segments that end on rows it_begin <= i < it_end of nray rays
+ * and ACCUMULATES into d_cnt (int64), d_time and d_wsum (fp64; NULL iff
+ * wcol < 0), each [nchan][ny][nx], and d_dropped[1] (int64): the caller zeroes
+ * them once, so time chunks and shards add up.  Row layouts and their argument
+ * rules are those of rwrt_ray_density.  d_ray[nray] (int64): ray j of the call
+ * is column d_ray[j] (a shard's rays in the whole set's arrays), NULL: column
+ * j; a ray whose column is outside [0, nacc_cols) is skipped.  d_chan
+ * [nacc_cols] (int32) is indexed by that column, NULL: channel 0.
+ *  d_prev[3][nacc_cols] (fp64): the carried previous row of every ray -- lon
+ *    (NaN: no valid previous row), lat, and the value of column wcol (0
+ *    without one).  The caller writes NaN once; every call loads a ray's
+ *    column, walks its rows and stores the last row, with lon = NaN if that
+ *    row was invalid.  It is a running state, not a sum: the calls for one ray
+ *    must deliver CONSECUTIVE rows in order -- each call's it_begin equals the
+ *    previous call's it_end (row 0, the initial row, is a call of its own with
+ *    it_begin = 0, which deposits nothing).  Nothing checks that on the
+ *    device.  Two rays must not share a column in one call.  A ray whose
+ *    channel is outside [0, nchan) is not walked and its column stays.
+ * One lane walks one ray and keeps the current cell's visits and sums in
+ * registers across segments (a ray ends a segment in the cell in which it
+ * starts the next), adding them to the map only when the cell changes: one
+ * 64-bit integer add and one or two hardware fp64 adds, no compare-exchange
+ * loop.  A constant tail of n rows is its first segment plus one update for
+ * the n - 1 segments of length zero.  cnt and dropped are exact; time and
+ * wsum depend on the arrival order in their last bits.
+ * RWRT_ERR_ARG before any HIP call: a NULL map, d_prev, d_cnt, d_time or
+ * d_dropped; d_wsum present without wcol or missing with it; nx, ny or nchan
+ * not positive; nchan*ny*nx >= 2^31; mode other than 0 or 2; max_cells < 1;
+ * need or wcol outside {-1, 2..6}; inv_dlon or inv_dlat not finite and
+ * positive; lon0 or lat0 not finite; wrapped with lon0 != 0; it_begin < 0;
+ * nacc_cols not covering the rays; the row arguments as for rwrt_ray_density.
+ * Asynchronous and ordered on `stream`; needs no rwrt_ctx.  nray == 0 is a
+ * no-op. */
+rwrt_status rwrt_ray_track(const rwrt_track_map* m, int64_t nray,
+                           int32_t it_begin, int32_t it_end,
+                           const double* d_rows, const int32_t* d_row_slot,
+                           const int32_t* d_tail_from, const double* d_tail_row,
+                           const int64_t* d_ray, int64_t nacc_cols, const int32_t* d_chan,
+                           double* d_prev, int64_t* d_cnt, double* d_time,
+                           double* d_wsum, int64_t* d_dropped, void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

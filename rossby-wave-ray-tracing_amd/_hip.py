@@ -21,6 +21,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_ray_initial", "rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails",
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
                "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival", "rwrt_ray_flux",
+               "rwrt_ray_track",
                "rwrt_wn_map", "rwrt_wn_fill",
                "rwrt_sh_filter",
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
@@ -80,6 +81,20 @@ class FluxMapC(ctypes.Structure):
 
 assert ctypes.sizeof(FluxMapC) == 72
 
+
+class TrackMapC(ctypes.Structure):
+    """``rwrt_track_map``: the map a ``rwrt_ray_track`` call deposits into
+    (``mode`` bit 1: unwrapped longitude window; ``need`` / ``wcol``: row
+    columns, -1 for none)."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nchan", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("need", ctypes.c_int32), ("wcol", ctypes.c_int32),
+                ("max_cells", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("lon0", ctypes.c_double), ("inv_dlon", ctypes.c_double),
+                ("lat0", ctypes.c_double), ("inv_dlat", ctypes.c_double)]
+
+
+assert ctypes.sizeof(TrackMapC) == 64
+
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
 NDIAG = 23     # RWRT_NDIAG: the planes of rwrt_bs_diag
 
@@ -114,6 +129,7 @@ def load():
     R = ctypes.POINTER(SummaryRegions)
     A = ctypes.POINTER(ArrivalMap)
     F = ctypes.POINTER(FluxMapC)
+    T = ctypes.POINTER(TrackMapC)
     sig = {
         "rwrt_pack_fields": [G, _P, _P, _P],
         "rwrt_mercator_point": [G, _P, _I64, _P, _P, _P, _P],
@@ -133,6 +149,7 @@ def load():
         "rwrt_ray_density": [M, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_arrival": [A, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_flux": [F, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
+        "rwrt_ray_track": [T, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_summary": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, R, _P, _P, _P],
         "rwrt_wn_map": [G, _P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_wn_fill": [_I32, _I32, _I32, _I32, _P, _P, _P],
