@@ -751,7 +751,13 @@ rwrt_status rwrt_kat_rk45(int32_t kind, int64_t ncol, const double* d_y0,
  * where that division is inside its exact range (DivGuard), else 0.0, and
  * 36/37 the jump mask's verdict (wr.py:844-850; 1.0: a jump) for a step of
  * (dlat, dlon) = (x, y) from (lon, lat) = (1.0, 0.6) rad at cut_off 0.05 rad,
- * 36 with the kernels' polynomial "no jump" shortcut, 37 without it.
+ * 36 with the kernels' polynomial "no jump" shortcut, 37 without it
+ * (38/39: unassigned, refused), 40 the lean RHS tail's leaf guard: 1.0 where
+ * the value x is admitted as leaf y (0 lons - lon0, 1 lat - lat0, 2 lat, 3 k,
+ * 4 l, 5 amp; the other leaves physical), else 0.0, 41 the shared reciprocal
+ * rcp2(x) itself, 42 the literal the kernels hold for rcp2(6.3712e6) and
+ * 43 1.0 where a packed background value x is inside the lean tier's window
+ * (0, or finite with an admitted exponent), else 0.0.
  * Lets the tests prove which operations are bit-exact on the GPU (IEEE
  * division, sqrt, fmod) and measure the last-bit agreement of the rest. */
 rwrt_status rwrt_selftest_math(int32_t kind, int64_t n, const double* d_x,

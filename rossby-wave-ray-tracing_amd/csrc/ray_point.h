@@ -154,13 +154,15 @@ struct Corners {
   unsigned key_x, key_y;   // x0 | x1 << 16, y0 | y1 << 16 (W, H < 2^16)
   unsigned pa, pb, pc, pd; // grid-point indices x * H + y of a, b, c, d
   unsigned oa, ob, oc, od; // element offsets of a, b, c, d from F.P
+  double dx, dy;           // lons - lon0, lat - lat0: the numerators of the cell coordinates
 };
 
 __device__ __forceinline__ Corners corners(const Field& F, double lon, double lat) {
   // lon arrives already reduced once (bs.py:519); interpolation.py:80 reduces again.
   const double lons = py_mod_2pi_again(lon);
   double x, y;
-  div2(lons - F.lon0, F.dlon, lat - F.lat0, F.dlat, x, y);
+  const double dx = lons - F.lon0, dy = lat - F.lat0;
+  div2(dx, F.dlon, dy, F.dlat, x, y);
   const int ix = floor_i32(x), iy = floor_i32(y);
   const int x0 = clip(ix, F.W - 1), x1 = clip(inc_i32(ix), F.W - 1);
   const int y0 = clip(iy, F.H - 1), y1 = clip(inc_i32(iy), F.H - 1);
@@ -169,6 +171,8 @@ __device__ __forceinline__ Corners corners(const Field& F, double lon, double la
   // (W, H < 2^24: 24-bit multiplies)
   const unsigned c0 = __umul24(x0, F.H), c1 = __umul24(x1, F.H);
   Corners k;
+  k.dx = dx;
+  k.dy = dy;
   k.pa = c0 + y1;
   k.pb = c1 + y1;
   k.pc = c0 + y0;

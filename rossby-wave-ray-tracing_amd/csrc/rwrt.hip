@@ -148,6 +148,20 @@ __device__ __forceinline__ double div_hw(double a, double b, double rb) {
   return r;
 }
 
+// The RHS's shared-reciprocal division ("Shared-reciprocal division" below
+// says when qdiv(n, d, rcp2(d)) == n / d).
+__device__ __forceinline__ double rcp2(double d) {
+  double r = __builtin_amdgcn_rcp(d);
+  double e = fma(-d, r, 1.0);
+  r = fma(r, e, r);
+  e = fma(-d, r, 1.0);
+  return fma(r, e, r);
+}
+__device__ __forceinline__ double qdiv(double n, double d, double r) {
+  const double q = n * r;
+  const double e = fma(-d, q, n);
+  return __builtin_amdgcn_div_fixup(fma(e, r, q), d, n);
+}
 // slot -> index in the reference 18-field stack (bs.py:349-368); qyx (10) and
 // the six third derivatives are never read on the hot path.
 __constant__ int kRefIndex[11] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11};
@@ -167,6 +181,7 @@ struct StaticBG {
   static constexpr bool kTimeVarying = false;
   Field F;
   const char* img = nullptr;   // cache image of F (cache_image_kernel; the run kernels' refills)
+  const int* range = nullptr;  // exponent range of F's values (cache_image_kernel; bg_lean)
   __device__ __forceinline__ void interp11(double lon, double lat, double, double g[11]) const {
     rwrt::interp11(F, py_mod_2pi(lon), lat, g);
   }
@@ -175,6 +190,11 @@ struct StaticBG {
     rwrt::interp4(F, py_mod_2pi(lon), lat, fu, fv, fqx, fqy);
   }
 };
+
+// StaticBG in a launch whose verdict is the lean RHS tail (bg_lean): the same
+// state and lookups; the type selects ray_rhs's tier at compile time, so that
+// a kernel holds one tier only (both in one ray loop: 8 % slower).
+struct LeanStaticBG : StaticBG {};
 
 // Lookups in two halves, begin() and end(): the RHS issues a lookup, computes
 // what does not depend on it (sin, cos, tan of lat), then collects it.  For
@@ -262,13 +282,93 @@ inline size_t cache_image_bytes(int64_t npts) { return (size_t)((npts + 63) / 64
 // (= p * 16 + (p >> 6) * 5 KiB: a shift, a 24-bit multiply, a shift-add)
 __device__ __forceinline__ unsigned img_offset(unsigned p) { return __umul24(p >> 6, kImgTile - 1024u) + p * 16u; }
 
-__global__ void cache_image_kernel(Field F, char* __restrict__ img) {
+// The exponent range of a packed state (the lean RHS tail's launch verdict,
+// bg_lean below): three ints, zeroed before the kernel that fills them --
+//   [0] kExpBias - (smallest frexp exponent of a nonzero finite value), 0: none
+//   [1] kExpBias + (largest one), 0: none
+//   [2] nonzero: some value is inf or NaN
+// both as maxima, so that zeroed memory is the neutral element.
+constexpr int kExpBias = 2048;
+constexpr int kRangeInts = 4;
+struct ExpRange {
+  int a = 0, b = 0, bad = 0;
+  __device__ __forceinline__ void see(double v) {
+    const int e = __builtin_amdgcn_frexp_exp(v);
+    const bool fin = fabs(v) < __builtin_inf();
+    if (fin && v != 0.0) {
+      a = ::max(a, kExpBias - e);
+      b = ::max(b, kExpBias + e);
+    }
+    bad |= fin ? 0 : 1;
+  }
+  // one atomic per wave and word, from vector code
+  __device__ __forceinline__ void publish(int* range) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      a = ::max(a, __shfl_xor(a, d));
+      b = ::max(b, __shfl_xor(b, d));
+      bad |= __shfl_xor(bad, d);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+      if (a) atomicMax(range + 0, a);
+      if (b) atomicMax(range + 1, b);
+      if (bad) atomicMax(range + 2, 1);
+    }
+  }
+};
+
+// The lean RHS tail's windows on frexp exponents (see "Shared-reciprocal
+// division" below; DESIGN.md section 4 derives them).  A value v with
+// exponent e has 2^(e-1) <= |v| < 2^e; 0, inf and NaN have e = 0, and every
+// window holds 0.
+constexpr int kLeafLo = -100;                  // lons - lon0, lat - lat0, lat, l, amp: from below
+constexpr int kLeafAmpHi = 100;                // amp: from above (lat and l: the RHS's own mask;
+                                               // the two differences: lons < 2 pi, |lat| < pi/2, kOrigin*)
+constexpr int kLeafKLo = -7, kLeafKHi = 19;    // k: denom = k^2 (1 + (l/k)^2)^2 stays in [2^-16, 2^100)
+constexpr int kBgLo = -250, kBgHi = 200;       // every nonzero packed value of the launch
+constexpr int kStepLo = -30, kStepHi = 2;      // dlon, dlat
+constexpr int kOriginLonHi = 3, kOriginLatHi = 1;   // lon0, lat0: |lons - lon0| < 16, |lat - lat0| < 4
+// the two leaves of the lookup: dx = lons - lon0, dy = lat - lat0 (corners())
+__device__ __forceinline__ bool cell_leaf_ok(double dx, double dy) {
+  const int ex = __builtin_amdgcn_frexp_exp(dx), ey = __builtin_amdgcn_frexp_exp(dy);
+  return ::min(ex, ey) >= kLeafLo;
+}
+// The launch's verdict (wave-uniform): the packed values' exponent range as
+// cache_image_kernel / bg_range_kernel left it, and the grid steps'.
+__device__ __forceinline__ bool bg_lean(const int* range, const Field& F) {
+  if (!range) return false;
+  const int a = range[0], b = range[1], bad = range[2];
+  const int es = __builtin_amdgcn_frexp_exp(F.dlon), et = __builtin_amdgcn_frexp_exp(F.dlat);
+  const bool ok = bad == 0 && (a == 0 || kExpBias - a >= kBgLo) && (b == 0 || b - kExpBias <= kBgHi) &&
+                  ::min(es, et) >= kStepLo && ::max(es, et) <= kStepHi &&
+                  __builtin_amdgcn_frexp_exp(F.lon0) <= kOriginLonHi &&
+                  __builtin_amdgcn_frexp_exp(F.lat0) <= kOriginLatHi;
+  return __builtin_amdgcn_readfirstlane((int)ok) != 0;
+}
+
+// (range: the three ints behind the image, zeroed by the caller)
+__global__ void cache_image_kernel(Field F, char* __restrict__ img, int* __restrict__ range) {
   const int64_t n = (int64_t)F.W * F.H * 6;
+  ExpRange R;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const unsigned p = (unsigned)(i / 6), q = (unsigned)(i - (int64_t)p * 6);
     const double2 v = reinterpret_cast<const double2*>(F.P + (size_t)p * kNF)[q];
     *reinterpret_cast<double2*>(img + img_offset(p) + q * 1024u) = v;
+    R.see(v.x);
+    R.see(v.y);
   }
+  R.publish(range);
+}
+// the same verdict for an entry point without an image (rwrt_rhs)
+__global__ void bg_range_kernel(Field F, int* __restrict__ range) {
+  const int64_t n = (int64_t)F.W * F.H * 6;
+  ExpRange R;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const double2 v = reinterpret_cast<const double2*>(F.P)[i];
+    R.see(v.x);
+    R.see(v.y);
+  }
+  R.publish(range);
 }
 
 struct CachedStaticBG {
@@ -282,6 +382,7 @@ struct CachedStaticBG {
 
   struct Pending {
     double wa, wb, wc, wd;
+    bool cell_ok;   // the cell coordinates' numerators are inside the lean tail's window (cell_leaf_ok)
   };
   __device__ __forceinline__ const double2& chunk(int j, int q) const {
     return *reinterpret_cast<const double2*>(wave_base + (j * 6 + q) * 1024 + lane16);
@@ -377,7 +478,7 @@ struct CachedStaticBG {
       key_x = k.key_x;
       key_y = k.key_y;
     }
-    return Pending{k.wa, k.wb, k.wc, k.wd};
+    return Pending{k.wa, k.wb, k.wc, k.wd, cell_leaf_ok(k.dx, k.dy)};
   }
   // fill(): independent work placed between the first reads and the first
   // blend (the reads' latency; nothing else is in flight there)
@@ -426,6 +527,18 @@ struct CachedStaticBG {
 __device__ __forceinline__ CachedStaticBG::Pending lookup_begin(const CachedStaticBG& B, double lon,
                                                                 double lat, double) {
   return B.begin(lon, lat);
+}
+// CachedStaticBG of a launch on the lean tier (as LeanStaticBG: the type is
+// the tier), with the lookup's overloads
+struct LeanCachedStaticBG : CachedStaticBG {};
+__device__ __forceinline__ CachedStaticBG::Pending lookup_begin(const LeanCachedStaticBG& B, double lon,
+                                                                double lat, double) {
+  return B.begin(lon, lat);
+}
+template <class Fill>
+__device__ __forceinline__ void lookup_end(const LeanCachedStaticBG& B, const CachedStaticBG::Pending& p,
+                                           double g[11], Fill&& fill) {
+  B.end(p, g, fill);
 }
 __device__ __forceinline__ void lookup_end(const CachedStaticBG& B,
                                            const CachedStaticBG::Pending& p, double g[11]) {
@@ -1265,21 +1378,41 @@ __device__ __forceinline__ void ugvg(double fu, double fv, double fqx, double fq
 // exponent is in [-899, 600] (|n| in [2^-900, 2^600)) or n is 0, inf or NaN
 // (v_div_fixup's cases, frexp exponent 0), and the divisor's in [-99, 100]
 // (tests/test_gpu_parity.py::test_device_math_exactness, kinds 34-35).
-// DivGuard collects those exponents; a lane outside the range recomputes the
-// RHS tail with IEEE divisions (rhs_tail<false>, a rarely taken branch).
+//
+// Three tiers decide that an evaluation is inside that range:
+//   lean     (static background, the launch's verdict bg_lean): the exponents
+//            of six per-lane leaves -- lons - lon0, lat - lat0, lat, k, l, amp
+//            (leaf_ok, kLeaf* above) -- with the exponent range of the
+//            launch's packed values, grid steps and origin (cache_image_kernel,
+//            kBg*, kStep*, kOrigin*) bound every numerator and divisor of the tail: every
+//            numerator is built from them with +, - and * only, a product's
+//            exponent is the sum of its factors', a nonzero sum is at least
+//            an ulp of its larger operand, and 0, inf and NaN are v_div_fixup's
+//            cases.  DESIGN.md section 4 has the table, tests/
+//            test_divguard_bounds.py propagates it.  13 VALU per evaluation
+//            (rhs_tail_lean).  The tier is the background's type
+//            (LeanStaticBG, LeanCachedStaticBG), so a kernel holds one tier:
+//            rk45_run_kernel<.., kLean> is launched beside the guarded one
+//            and the launch's verdict ends one of the two at its entry.
+//   guarded  (every other background, or a launch whose values leave the
+//            window): DivGuard collects the exponent of every numerator and
+//            divisor, about 48 VALU per evaluation (rhs_tail_fast).
+//   IEEE     a lane that either guard refuses, or inside the Mercator pole
+//            band, recomputes the tail with IEEE divisions (rhs_tail_ieee, a
+//            rarely taken branch).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double rcp2(double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  double e = fma(-d, r, 1.0);
-  r = fma(r, e, r);
-  e = fma(-d, r, 1.0);
-  return fma(r, e, r);
+// The lean tier's leaf guard (windows: kLeaf* above, beside the background's).
+// cell_ok: cell_leaf_ok of the lookup's two numerators.  lat and l are bounded
+// from above by the RHS's own mask (|lat| >= pi/2 or |l| >= 100: l arrives as
+// NaN then, and every output is NaN whatever a division rounds to).
+__device__ __forceinline__ bool leaf_ok(bool cell_ok, double lat, double k, double l, double amp) {
+  const int ea = __builtin_amdgcn_frexp_exp(amp), ek = __builtin_amdgcn_frexp_exp(k);
+  const int lo = ::min(::min(__builtin_amdgcn_frexp_exp(lat), __builtin_amdgcn_frexp_exp(l)), ea);
+  return cell_ok && lo >= kLeafLo && ea <= kLeafAmpHi &&
+         (unsigned)(ek - kLeafKLo) <= (unsigned)(kLeafKHi - kLeafKLo);
 }
-__device__ __forceinline__ double qdiv(double n, double d, double r) {
-  const double q = n * r;
-  const double e = fma(-d, q, n);
-  return __builtin_amdgcn_div_fixup(fma(e, r, q), d, n);
-}
+// rcp2(kREarth), bit for bit (rwrt_selftest_math kinds 41/42 hold the two together)
+constexpr double kRcpREarth = 0x1.510fa3eaca281p-23;
 struct DivGuard {
   int nlo = 0, nhi = 0, dlo = 0, dhi = 0;   // exponent range seen (0: neutral)
   __device__ __forceinline__ void num(double n) {
@@ -1389,6 +1522,53 @@ __device__ __forceinline__ bool rhs_tail_fast(const double g[11], const Merc& M,
   return G.ok() & (M.m == 1.0);
 }
 
+// The lean tier: kap_terms_r and rhs_tail_fast, operation for operation,
+// without DivGuard -- the caller's leaf_ok and the launch's bg_lean have
+// bounded every operand (and M.m == 1: off the pole band).
+__device__ __forceinline__ KapTermsR kap_terms_lean(double k, double l) {
+  KapTermsR w;
+  w.kap = qdiv(l, k, rcp2(k));
+  w.kap2 = w.kap * w.kap;
+  w.kap1 = 1.0 + w.kap2;
+  w.kk = (k * k) * w.kap1;
+  w.denom = w.kk * w.kap1;
+  w.rkk = rcp2(w.kk);
+  w.rk1 = rcp2(w.kap1);
+  w.rden = rcp2(w.denom);
+  return w;
+}
+__device__ __forceinline__ void rhs_tail_lean(const double g[11], double s, double c, double tn, double kx,
+                                              const KapTermsR& kw, double amp, double* dy, double& ug,
+                                              double& vg) {
+  const double fu = g[F_U], fv = g[F_V];
+  const double rc = rcp2(c);
+  const double fmu = qdiv(fu, c, rc), fmv = qdiv(fv, c, rc);
+  const double fmux = qdiv(g[F_UX], c, rc), fmvx = qdiv(g[F_VX], c, rc);
+  const double fmuy = g[F_UY] + tn * fu, fmvy = g[F_VY] + tn * fv;
+  const double fmqx = g[F_QX], fmqy = g[F_QY] * c, fmqxx = g[F_QXX];
+  const double fmqyx = g[F_QXY] * c, fmqxy = fmqyx;
+  const double fmqyy = ((g[F_QYY] * c) - (g[F_QY] * s)) * c;
+  // cal_ugvg
+  const double kap = kw.kap, kap2 = kw.kap2;
+  ug = fmu + qdiv(((1.0 - kap2) * fmqy) - ((2.0 * kap) * fmqx), kw.denom, kw.rden);
+  vg = fmv + qdiv(((2.0 * kap) * fmqy) + ((1.0 - kap2) * fmqx), kw.denom, kw.rden);
+  // core_diffun
+  const double qk = qdiv(kap * fmqxx - fmqyx, kw.kk, kw.rkk);
+  const double ql = qdiv(kap * fmqxy - fmqyy, kw.kk, kw.rkk);
+  const double dzwn = (-kx) * ((fmux + kap * fmvx) + qk);
+  const double dmwn = (-kx) * ((fmuy + kap * fmvy) + ql);
+  const double damp1 = qdiv(2.0 * ((fmux + fmvy) + kap * (fmvx + fmuy)), kw.kap1, kw.rk1);
+  const double damp2 = qdiv(2.0 * (kap * (fmqxx - fmqyy) + (kap2 - 1.0) * fmqxy), kw.denom, kw.rden);
+  const double damp3 = (-2.0 * s) * fmv;
+  const double damp = (damp1 + damp2) + damp3;
+  const double rR = kRcpREarth;   // == rcp2(kREarth)
+  dy[0] = qdiv(ug, kREarth, rR);
+  dy[1] = qdiv(vg * c, kREarth, rR);
+  dy[2] = qdiv(dzwn, kREarth, rR);
+  dy[3] = qdiv(dmwn, kREarth, rR);
+  dy[4] = qdiv(damp * amp, kREarth, rR);
+}
+
 // rhs_tail_fast for a lane pair's split outputs: the same operations, but
 // each lane divides only the numerators of its own variables by R -- the
 // lower lane dy0, dy2, the upper one dy1, dy3 (the same operation shape on
@@ -1431,9 +1611,25 @@ __device__ __forceinline__ bool rhs_tail_fast_pair(const double g[11], const Mer
 // aux (optional) receives {ug, vg, cos(lat)} of this evaluation -- exactly what
 // the per-interval post-processing recomputes at the same position
 // (wr.py:844, 856-865) -- or NaN for a masked ray (no values computed).
-template <class BG>
-__device__ __forceinline__ void ray_rhs(const BG& B, double t, const double* y, double* dy,
-                                        double* aux = nullptr) {
+// The backgrounds with a lean tier (the static state's), and the lean tail's
+// two leaves of their lookup.
+template <class BG> struct HasLean : std::false_type {};
+template <> struct HasLean<LeanStaticBG> : std::true_type {};
+template <> struct HasLean<LeanCachedStaticBG> : std::true_type {};
+__device__ __forceinline__ bool pending_cell_ok(const LeanCachedStaticBG&, const CachedStaticBG::Pending& p) {
+  return p.cell_ok;
+}
+__device__ __forceinline__ bool pending_cell_ok(const LeanStaticBG& B, const PendingPoint& p) {
+  return cell_leaf_ok(py_mod_2pi_again(py_mod_2pi(p.lon)) - B.F.lon0, p.lat - B.F.lat0);   // as corners()
+}
+template <class BG, class P>
+__device__ __forceinline__ bool pending_cell_ok(const BG&, const P&) {
+  return false;
+}
+
+// kLean: the lean tier (the background's type: ray_rhs below)
+template <bool kLean, class BG>
+__device__ __forceinline__ void ray_rhs_tier(const BG& B, double t, const double* y, double* dy, double* aux) {
   const double lon = y[0], lat = y[1], kx = y[2];
   // wr.py:508-514: a masked ray's l is NaN; every derivative of it is then NaN
   // (each one depends on kap = l / k), as the reference's NaN fill
@@ -1456,11 +1652,26 @@ __device__ __forceinline__ void ray_rhs(const BG& B, double t, const double* y, 
   MARK("r_trig_end");
   __builtin_amdgcn_sched_barrier(0);
   // the wavenumber terms (k, l only) under the cell cache's first reads (+0.3 %, r4e)
-  lookup_end(B, pending, g, [&] { kw = kap_terms_r(kx, ky, G); MARK("r_kap"); });
+  lookup_end(B, pending, g, [&] {
+    if constexpr (kLean) kw = kap_terms_lean(kx, ky);
+    else kw = kap_terms_r(kx, ky, G);
+    MARK("r_kap");
+  });
   MARK("r_lookup_end");
   const Merc M = merc_factors(lat, c, s);
   double ug, vg;
-  if (RARE(!rhs_tail_fast(g, M, s, c, tn, kx, kw, G, amp, dy, ug, vg))) {
+  if constexpr (kLean) {
+    // the six leaves (the lookup's two: pending) and the pole band decide
+    // before the tail: a refused lane takes the IEEE tail alone
+    // (a masked ray needs no upper bound on lat or l: its l is NaN here, and
+    // every output NaN whatever the divisions round to)
+    const bool ok = leaf_ok(pending_cell_ok(B, pending), lat, kx, ky, amp) && M.m == 1.0;
+    rhs_tail_lean(g, s, c, tn, kx, kw, amp, dy, ug, vg);
+    if (RARE(!ok)) {
+      asm volatile("");   // a leaf outside its window, or the pole band (rare branch)
+      rhs_tail_ieee(g, M, s, c, tn, kx, ky, amp, dy, ug, vg);
+    }
+  } else if (RARE(!rhs_tail_fast(g, M, s, c, tn, kx, kw, G, amp, dy, ug, vg))) {
     asm volatile("");   // an operand outside qdiv's exact range, or the pole band (rare branch)
     rhs_tail_ieee(g, M, s, c, tn, kx, ky, amp, dy, ug, vg);
   }
@@ -1470,6 +1681,11 @@ __device__ __forceinline__ void ray_rhs(const BG& B, double t, const double* y, 
     aux[1] = vg;
     aux[2] = bad ? kNaN : c;
   }
+}
+template <class BG>
+__device__ __forceinline__ void ray_rhs(const BG& B, double t, const double* y, double* dy,
+                                        double* aux = nullptr) {
+  ray_rhs_tier<HasLean<BG>::value>(B, t, y, dy, aux);
 }
 
 // ray_rhs for a lane pair (PairVaryingBG64: lanes L and L + 32 hold one ray):
@@ -2201,15 +2417,18 @@ __global__ void mercator_kernel(Field F, int64_t n, const double* __restrict__ l
   }
 }
 
-__global__ void rhs_kernel(Field F, int64_t n, const double* __restrict__ y,
+// (range: the packed values' exponent range, bg_range_kernel -- the lean tier's verdict)
+__global__ void rhs_kernel(Field F, const int* __restrict__ range, int64_t n, const double* __restrict__ y,
                            double* __restrict__ dydt) {
   nm_stage<NM_SINCOS | NM_TAN>();
+  const bool lean = bg_lean(range, F);   // (wave-uniform)
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     double yy[5], d[5];
 #pragma unroll
     for (int v = 0; v < 5; ++v) yy[v] = y[v * n + i];
-    ray_rhs(StaticBG{F}, 0.0, yy, d);
+    if (lean) ray_rhs(LeanStaticBG{{F}}, 0.0, yy, d);
+    else ray_rhs(StaticBG{F}, 0.0, yy, d);
 #pragma unroll
     for (int v = 0; v < 5; ++v) dydt[v * n + i] = d[v];
   }
@@ -2874,7 +3093,7 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
   int32_t it = 0, nanrow = 0, wpos = 0;   // (wpos: the ray's queue position, kTrace only)
   double prev_lon = 0.0, prev_lat = 0.0, cos_prev = 0.0;
   // drain-time hand-off (the static state's ray loop): see below the loop
-  constexpr bool kHandoff = std::is_same<LBG, CachedStaticBG>::value && !kReplica && !kPair && !kTrace;
+  constexpr bool kHandoff = std::is_base_of<CachedStaticBG, LBG>::value && !kReplica && !kPair && !kTrace;
   bool handoff = false;
   // above frozen_fill_kernel's waves (priority 0) sharing the SIMD: the
   // fill takes the issue cycles the ray loop leaves idle
@@ -3072,9 +3291,18 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
   }
 }
 
-template <class BG, bool kTrace = false>
+// kLean (static state): the kernel of the launches whose verdict is the lean
+// RHS tail.  The verdict is on the device (cache_image_kernel, bg_lean), so
+// the host launches both kernels and the one of the other tier ends at once.
+template <class BG, bool kTrace = false, bool kLean = false>
 __global__ void __launch_bounds__(256, 1) __attribute__((aligned(RWRT_RUN_ALIGN)))
 rk45_run_kernel(RunArgs<BG> a) {
+  static_assert(!kLean || std::is_same<BG, StaticBG>::value, "the lean tier is the static state's");
+#ifndef RWRT_ANALYZE_HOT   // (the analysis build compiles each tier's loop as the common path)
+  if constexpr (std::is_same<BG, StaticBG>::value) {
+    if (bg_lean(a.B.range, a.B.F) != kLean) return;   // (launch-uniform)
+  }
+#endif
   nm_stage<NM_ALL>();
   // all LDS in one array: the stages (5 x 5 doubles per lane) then the lookup cache
   constexpr int kKBytes = 5 * 5 * 256 * 8;
@@ -3113,7 +3341,11 @@ rk45_run_kernel(RunArgs<BG> a) {
       return;
     }
   }
-  run_rays<BG, typename LaneBG<BG>::type, kTrace, false>(a, LaneBG<BG>::make(a.B, smem + kKBytes), smem, -1);
+  if constexpr (kLean)
+    run_rays<BG, LeanCachedStaticBG, kTrace, false>(a, LeanCachedStaticBG{LaneBG<BG>::make(a.B, smem + kKBytes)}, smem,
+                                                    -1);
+  else
+    run_rays<BG, typename LaneBG<BG>::type, kTrace, false>(a, LaneBG<BG>::make(a.B, smem + kKBytes), smem, -1);
 }
 
 // ---------------------------------------------------------------------------
@@ -3295,6 +3527,19 @@ __global__ void math_kernel(int kind, int64_t n, const double* __restrict__ x,
       G.num(a);
       G.den(b);
       r = G.ok() ? 1.0 : 0.0;
+    } break;
+    case 40: {   // the lean tail's leaf guard on a as leaf b (0 dx, 1 dy, 2 lat, 3 k, 4 l, 5 amp), the others physical
+      const int leaf = (int)b;
+      double v[6] = {1.0, 1.0, 0.5, 3.0, 2.0, 1.0};
+      if (leaf >= 0 && leaf < 6) v[leaf] = a;
+      const bool masked = fabs(v[2]) >= kHalfPi || fabs(v[4]) >= 100.0;   // as ray_rhs
+      r = leaf_ok(cell_leaf_ok(v[0], v[1]), v[2], v[3], masked ? kNaN : v[4], v[5]) ? 1.0 : 0.0;
+    } break;
+    case 41: r = rcp2(a); break;
+    case 42: r = kRcpREarth; break;
+    case 43: {   // 1 where a packed value a leaves the launch inside the lean tier's window (ExpRange, bg_lean)
+      const int e = __builtin_amdgcn_frexp_exp(a);
+      r = (a == 0.0 || (fabs(a) < __builtin_inf() && e >= kBgLo && e <= kBgHi)) ? 1.0 : 0.0;
     } break;
     default: r = kNaN; break;   // (unreachable: rwrt_selftest_math rejects other kinds)
   }
@@ -3726,8 +3971,10 @@ rwrt_status ctx_flags(rwrt_ctx* c, int64_t nray) {
 // the previous call of the context, which may still read the old image, is
 // finished on the device by then).  Rebuilt every call, so a caller may change
 // the packed state between calls; ~1 MB at 2.5 degrees.
-rwrt_status ctx_image(rwrt_ctx* c, const Field& F, hipStream_t stream, const char** out) {
-  const size_t need = cache_image_bytes((int64_t)F.W * F.H);
+rwrt_status ctx_image(rwrt_ctx* c, const Field& F, hipStream_t stream, const char** out,
+                      const int** range = nullptr) {
+  // the values' exponent range (bg_lean) behind the image, zeroed for the kernel's maxima
+  const size_t image = cache_image_bytes((int64_t)F.W * F.H), need = image + kRangeInts * sizeof(int);
   if (need > c->img_cap) {
     if (c->img) {
       if ((c->used && hipEventSynchronize(c->done) != hipSuccess) || hipFree(c->img) != hipSuccess)
@@ -3739,9 +3986,13 @@ rwrt_status ctx_image(rwrt_ctx* c, const Field& F, hipStream_t stream, const cha
       return fail(RWRT_ERR_HIP, "cache image allocation failed%s");
     c->img_cap = need;
   }
+  int* r = reinterpret_cast<int*>(c->img + image);
+  if (hipMemsetAsync(r, 0, kRangeInts * sizeof(int), stream) != hipSuccess)
+    return check_launch("hipMemsetAsync(exponent range)");
   hipLaunchKernelGGL(cache_image_kernel, dim3(grid_for((int64_t)F.W * F.H * 6, 256)), dim3(256), 0, stream,
-                     F, c->img);
+                     F, c->img, r);
   *out = c->img;
+  if (range) *range = r;
   return check_launch("cache_image_kernel");
 }
 
@@ -3856,7 +4107,7 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
       }))
     return s;
   if constexpr (std::is_same<BG, StaticBG>::value) {
-    if (rwrt_status s = ctx_image(ctx, B.F, st, &a.B.img)) return s;
+    if (rwrt_status s = ctx_image(ctx, B.F, st, &a.B.img, &a.B.range)) return s;
   }
   // latency mode in the run kernel's first team_blocks blocks (quad_rays):
   // one grid, so they are placed beside the persistent blocks whatever the
@@ -3871,10 +4122,15 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   if (nray > n_heavy || team_blocks) {
     const int64_t grid = team_blocks + (nray > n_heavy ? blocks : 0);
     if (a.trace && std::is_same<BG, StaticBG>::value) {
-      if constexpr (std::is_same<BG, StaticBG>::value)
+      if constexpr (std::is_same<BG, StaticBG>::value) {
         hipLaunchKernelGGL((rk45_run_kernel<BG, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((rk45_run_kernel<BG, true, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
+      }
     } else {
       hipLaunchKernelGGL(rk45_run_kernel<BG>, dim3((unsigned)grid), dim3(256), 0, st, a);
+      // the static state's two tiers: the launch's verdict ends one of the two at its entry
+      if constexpr (std::is_same<BG, StaticBG>::value)
+        hipLaunchKernelGGL((rk45_run_kernel<BG, false, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
     }
     if (rwrt_status s = check_launch("rk45_run_kernel")) return s;
   }
@@ -4272,9 +4528,25 @@ rwrt_status rwrt_rhs(const rwrt_grid* g, const double* d_packed, int64_t n, cons
   if (rwrt_status s = make_field(g, d_packed, F)) return s;
   if (n < 0 || (n > 0 && (!d_y || !d_dydt))) return fail(RWRT_ERR_ARG, "bad state arrays%s");
   if (n == 0) return RWRT_OK;
-  hipLaunchKernelGGL(rhs_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, F, n,
-                     d_y, d_dydt);
-  return check_launch("rhs_kernel");
+  // the lean tier's verdict on this state, as a ray run gets it from its cache
+  // image: reduced on the stream into stream-ordered memory (no host wait)
+  hipStream_t st = (hipStream_t)stream;
+  int* range = nullptr;
+  if (hipMallocAsync(reinterpret_cast<void**>(&range), kRangeInts * sizeof(int), st) != hipSuccess)
+    return fail(RWRT_ERR_HIP, "exponent-range allocation failed%s");
+  rwrt_status rs = RWRT_OK;
+  if (hipMemsetAsync(range, 0, kRangeInts * sizeof(int), st) != hipSuccess) {
+    rs = check_launch("hipMemsetAsync(exponent range)");
+  } else {
+    hipLaunchKernelGGL(bg_range_kernel, dim3(grid_for((int64_t)F.W * F.H * 6, 256)), dim3(256), 0, st, F, range);
+    rs = check_launch("bg_range_kernel");
+  }
+  if (rs == RWRT_OK) {
+    hipLaunchKernelGGL(rhs_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, F, range, n, d_y, d_dydt);
+    rs = check_launch("rhs_kernel");
+  }
+  if (hipFreeAsync(range, st) != hipSuccess && rs == RWRT_OK) rs = check_launch("hipFreeAsync(exponent range)");
+  return rs;
 }
 
 rwrt_status rwrt_dp54_attempt(const rwrt_grid* g, const double* d_packed, int64_t n,
@@ -4583,12 +4855,12 @@ rwrt_status rwrt_kat_rk45(int32_t kind, int64_t ncol, const double* d_y0, int32_
 
 rwrt_status rwrt_selftest_math(int32_t kind, int64_t n, const double* d_x, const double* d_y,
                                double* d_out, void* stream) {
-  if (n < 0 || kind < 0 || kind > 37 || (n > 0 && (!d_x || !d_out)))
+  if (n < 0 || kind < 0 || kind > 43 || kind == 38 || kind == 39 || (n > 0 && (!d_x || !d_out)))
     return fail(RWRT_ERR_ARG, "bad selftest arguments%s");
   if (kind >= 17 && kind <= 22)   // retired device-libm restatements: never alias another kind
     return fail(RWRT_ERR_ARG, "selftest kinds 17-22 are retired%s");
   if (n == 0) return RWRT_OK;
-  if (kind >= 36) {
+  if (kind == 36 || kind == 37) {
     if (!d_y) return fail(RWRT_ERR_ARG, "selftest kinds 36/37 need d_y%s");
     hipLaunchKernelGGL(jump_verdict_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, kind,
                        n, d_x, d_y, d_out, haversine_cut(0.05));

@@ -8,7 +8,7 @@ common path, so its static instruction count is what a wave issues per attempt
 branches, reported separately).  Used to A/B instruction-count changes without
 a GPU; the product build is unaffected.
 
-  python tools/hot_count.py [--defs "-DX=1 ..."] [--kernel static|c5_64|c5_32] [--asm out.s]
+  python tools/hot_count.py [--defs "-DX=1 ..."] [--kernel static|guarded|c5_64|c5_32] [--asm out.s]
 """
 import argparse
 import collections
@@ -20,10 +20,13 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc")
+# rk45_run_kernel<BG, kTrace = false, kLean>: "static" is the lean tier's kernel (the
+# one a C3 launch runs), "guarded" the DivGuard tier's
 KERNELS = {
-    "static": "_ZN4rwrt15rk45_run_kernelINS_8StaticBGELb0EEEvNS_7RunArgsIT_EE",
-    "c5_64": "_ZN4rwrt15rk45_run_kernelINS_9VaryingBGIdEELb0EEEvNS_7RunArgsIT_EE",
-    "c5_32": "_ZN4rwrt15rk45_run_kernelINS_9VaryingBGIfEELb0EEEvNS_7RunArgsIT_EE",
+    "static": "_ZN4rwrt15rk45_run_kernelINS_8StaticBGELb0ELb1EEEvNS_7RunArgsIT_EE",
+    "guarded": "_ZN4rwrt15rk45_run_kernelINS_8StaticBGELb0ELb0EEEvNS_7RunArgsIT_EE",
+    "c5_64": "_ZN4rwrt15rk45_run_kernelINS_9VaryingBGIdEELb0ELb0EEEvNS_7RunArgsIT_EE",
+    "c5_32": "_ZN4rwrt15rk45_run_kernelINS_9VaryingBGIfEELb0ELb0EEEvNS_7RunArgsIT_EE",
 }
 
 

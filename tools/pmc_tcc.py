@@ -19,7 +19,9 @@ def main():
         if "rk45_run_kernel" not in r["Kernel_Name"]:
             continue
         tot[r["Counter_Name"]] = tot.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
-        seen.add(r.get("Dispatch_Id") or r.get("Correlation_Id"))
+        # one per call: the static state's other RHS tier (<.., kLean = true>) is a second dispatch
+        if ", true>(" not in r["Kernel_Name"]:
+            seen.add(r.get("Dispatch_Id") or r.get("Correlation_Id"))
     n = max(len(seen), 1)
     hit, miss, rd = (tot.get(k, 0.0) / n for k in ("TCC_HIT_sum", "TCC_MISS_sum", "TCC_EA0_RDREQ_sum"))
     res = {"kernel": "rk45_run_kernel", "dispatches": len(seen), "tcc_hit_per_launch": hit,

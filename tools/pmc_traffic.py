@@ -18,6 +18,13 @@ import sys
 KERNELS = ("rk45_run_kernel", "frozen_fill_kernel", "frozen_flag_kernel", "frozen_tail_kernel")
 
 
+def is_launch(name):
+    """One per rwrt_rk45_run call: the static state launches rk45_run_kernel once
+    per RHS tier (<.., kLean = false> and <.., true>; the tier the device did not
+    pick returns at its entry), every state the kLean = false one."""
+    return "rk45_run_kernel" in name and ", true>(" not in name
+
+
 def per_launch(d, counter):
     """Bytes per rwrt_rk45_run call: the calls' kernels summed, divided over
     the rk45_run_kernel dispatches (one per call)."""
@@ -25,7 +32,7 @@ def per_launch(d, counter):
     for r in csv.DictReader(open(f"{d}/run_counter_collection.csv")):
         if r["Counter_Name"] == counter and any(k in r["Kernel_Name"] for k in KERNELS):
             total += float(r["Counter_Value"]) * 1024.0
-            launches += "rk45_run_kernel" in r["Kernel_Name"]
+            launches += is_launch(r["Kernel_Name"])
     return [total / max(launches, 1)] * launches
 
 
@@ -38,7 +45,7 @@ def by_kernel(d, counter):
         k = next((k for k in KERNELS if k in r["Kernel_Name"]), None)
         if k:
             tot[k] = tot.get(k, 0.0) + float(r["Counter_Value"]) * 1024.0
-            launches += k == "rk45_run_kernel"
+            launches += is_launch(r["Kernel_Name"])
     return {k: v / max(launches, 1) for k, v in tot.items()}
 
 

@@ -18,6 +18,14 @@ import sys
 KERNEL = "rk45_run_kernel"
 
 
+def is_launch(name):
+    """One per rwrt_rk45_run call: the static state launches rk45_run_kernel once
+    per RHS tier (<.., kLean = false> and <.., true>; the tier the device did not
+    pick returns at its entry), every state the kLean = false one."""
+    return "rk45_run_kernel" in name and ", true>(" not in name
+
+
+
 def main():
     d, log, out = sys.argv[1:4]
     per = {}
@@ -25,14 +33,15 @@ def main():
         if KERNEL not in r["Kernel_Name"]:
             continue
         k = r["Dispatch_Id"]
-        e = per.setdefault(k, {"t": (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-9})
+        e = per.setdefault(k, {"t": (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-9,
+                               "launch": is_launch(r["Kernel_Name"])})
         e[r["Counter_Name"]] = e.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
     bench = None
     for line in open(log):
         if line.startswith("{"):
             bench = json.loads(line)
     launches = list(per.values())
-    n = len(launches)
+    n = sum(x["launch"] for x in launches)   # (both tiers' dispatches summed per call)
     tot = lambda c: sum(x.get(c, 0.0) for x in launches)
     t = tot("t")
     clock = tot("GRBM_GUI_ACTIVE") / 8.0 / t
