@@ -42,8 +42,9 @@ extern "C" {
                                   (rwrt_sh_filter), the arrival-time maps
                                   (rwrt_ray_arrival), the basic-state diagnostics
                                   (rwrt_bs_diag), the wave-ray flux maps
-                                  (rwrt_ray_flux) and the residence-time maps along ray
-                                  segments (rwrt_ray_track): no earlier signature or layout
+                                  (rwrt_ray_flux), the residence-time maps along ray
+                                  segments (rwrt_ray_track) and the gate-crossing maps
+                                  (rwrt_ray_cross): no earlier signature or layout
                                   changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
@@ -615,6 +616,88 @@ rwrt_status rwrt_ray_track(const rwrt_track_map* m, int64_t nray,
                            const int64_t* d_ray, int64_t nacc_cols, const int32_t* d_chan,
                            double* d_prev, int64_t* d_cnt, double* d_time,
                            double* d_wsum, int64_t* d_dropped, void* stream);
+
+/* ABI 5, additive: gate-crossing maps.  The maps above reduce per lon-lat
+ * box; a line has no area.  Here every passage of a ray's segment (two
+ * consecutive valid rows) through a GATE -- a latitude circle or a meridian --
+ * is counted by direction, binned along the gate, timed, and recorded per ray.
+ * The definition is cross.reference_cross (Python); csrc/cross_lines.h
+ * restates it.  Every operation is one rounded fp64 + - * / or a floor, no
+ * FMA, IEEE division.
+ *
+ * kind 0, latitude circle lat = pos: s(lat) = (lat >= pos); the segment
+ *   crosses iff s0 != s1, in direction 0 (northward) iff s1, else 1;
+ *   t = (pos - lat0) / (lat1 - lat0); lon_c = lon0 + t * (lon1 - lon0); bin
+ *   min(floor(lam * inv_d), nbin - 1), lam = (lon_c % 2 pi) % 2 pi (Python's
+ *   float %, as rwrt_ray_density wraps); org is 0.
+ * kind 1, meridian lon = pos + 2 pi n, 0 <= pos < 2 pi: u = lon - pos,
+ *   m = floor(u * (1 / (2 pi))) -- lon is never wrapped; the segment crosses iff
+ *   m0 != m1, in direction 0 (eastward) iff m1 > m0, else 1.  It is DROPPED
+ *   for that gate -- d_dropped += 1 and nothing else -- iff |m0| > 2^30,
+ *   |m1| > 2^30 or |m1 - m0| > 1, compared in fp64.  Otherwise
+ *   G = max(m0, m1) * (2 pi), t = (G - u0) / (u1 - u0) clamped to [0, 1],
+ *   lat_c = lat0 + t * (lat1 - lat0), bin floor((lat_c - org) * inv_d), in
+ *   the map iff 0 <= bin < nbin.
+ * A row is valid as for rwrt_ray_track: lon, lat and the columns need / wcol
+ * finite; segment i joins rows i-1 and i and is considered iff both are valid
+ * and the ray's channel c is in [0, nchan).  A crossing of gate g in direction
+ * d on segment i happens at tc = (double)(i - 1) + t rows, in the window
+ * w = (i - 1) / window_rows (0 without windows).  Per ray, always:
+ * ncross[g][d] += 1, tfirst[g][d] = tc if it was NaN.  Per bin, when the
+ * crossing is in the map: cnt[w][g][d][c][bin] += 1, tsum += tc and, with
+ * wcol >= 0, wsum += v0 + t * (v1 - v0). */
+#define RWRT_CROSS_MAXGATE 8
+typedef struct {
+  int32_t kind, reserved;   /* 0: latitude circle, 1: meridian */
+  double pos;               /* rad; a meridian's in [0, 2 pi) */
+  double org, inv_d;        /* the bins along the gate: nbin over longitude (org 0, nbin / (2 pi))
+                               resp. over latitude (lat0, nbin / (lat1 - lat0)) */
+} rwrt_cross_gate;          /* 32 bytes */
+
+typedef struct {
+  int32_t ngate, nbin, nchan;
+  int32_t need, wcol;       /* row columns, -1 (none) or 2..6: must be finite / is interpolated */
+  int32_t window_rows, nwin;   /* 0 and 1: no time windows */
+  int32_t reserved;
+  rwrt_cross_gate gate[RWRT_CROSS_MAXGATE];
+} rwrt_cross_map;           /* 288 bytes */
+
+/* Finds the crossings of the segments that end on rows it_begin <= i < it_end
+ * of nray rays and ACCUMULATES into d_cnt (int64), d_tsum and d_wsum (fp64;
+ * NULL iff wcol < 0), each [nwin][ngate][2][nchan][nbin], d_dropped[1] (int64)
+ * and, unless both are NULL (maps only), d_ncross (int32) and d_tfirst (fp64),
+ * each [ngate][2][nacc_cols]: the caller zeroes the maps, d_dropped and
+ * d_ncross and writes NaN into d_tfirst and d_prev once, so time chunks and
+ * shards add up.  Row layouts, d_ray, d_chan (indexed by column) and d_prev
+ * [3][nacc_cols] -- the carried previous row, a running state fed CONSECUTIVE
+ * rows, row 0 in a call of its own -- are those of rwrt_ray_track; a ray whose
+ * channel is outside [0, nchan) is not walked and its columns stay.
+ * One lane walks one ray; a row's side of every gate (s, or m) is computed
+ * once and carried to the next row, and only where two sides differ are the
+ * division, the interpolation and the atomics made: one 64-bit integer add and
+ * one or two hardware fp64 adds, no compare-exchange loop; the ray's own
+ * column of d_ncross / d_tfirst takes plain loads and stores.  A constant tail
+ * is its first row: segments of length zero cross nothing.  cnt, ncross and
+ * dropped are exact, tfirst is written in row order and equals the definition
+ * bit for bit; tsum and wsum depend on the arrival order in their last bits.
+ * RWRT_ERR_ARG before any HIP call: a NULL map, d_prev, d_cnt, d_tsum or
+ * d_dropped; d_wsum present without wcol or missing with it; exactly one of
+ * d_ncross and d_tfirst; ngate outside 1..8; nbin or nchan not positive;
+ * nwin*ngate*2*nchan*nbin >= 2^31; kind other than 0 or 1; pos or org not
+ * finite; inv_d not finite and positive; a latitude circle with org != 0; a
+ * meridian's pos outside [0, 2 pi); need or wcol outside {-1, 2..6};
+ * window_rows < 0, nwin < 1, window_rows == 0 with nwin != 1, or it_end - 1 >
+ * nwin * window_rows with windows; it_begin < 0; nacc_cols not covering the
+ * rays; the row arguments as for rwrt_ray_density.  Asynchronous and ordered
+ * on `stream`; needs no rwrt_ctx.  nray == 0 is a no-op. */
+rwrt_status rwrt_ray_cross(const rwrt_cross_map* m, int64_t nray,
+                           int32_t it_begin, int32_t it_end,
+                           const double* d_rows, const int32_t* d_row_slot,
+                           const int32_t* d_tail_from, const double* d_tail_row,
+                           const int64_t* d_ray, int64_t nacc_cols, const int32_t* d_chan,
+                           double* d_prev, int64_t* d_cnt, double* d_tsum,
+                           double* d_wsum, int64_t* d_dropped,
+                           int32_t* d_ncross, double* d_tfirst, void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

@@ -21,7 +21,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_ray_initial", "rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails",
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
                "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival", "rwrt_ray_flux",
-               "rwrt_ray_track",
+               "rwrt_ray_track", "rwrt_ray_cross",
                "rwrt_wn_map", "rwrt_wn_fill",
                "rwrt_sh_filter",
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
@@ -95,6 +95,26 @@ class TrackMapC(ctypes.Structure):
 
 assert ctypes.sizeof(TrackMapC) == 64
 
+CROSS_MAXGATE = 8    # RWRT_CROSS_MAXGATE
+
+
+class CrossGateC(ctypes.Structure):
+    """``rwrt_cross_gate``: a latitude circle (``kind`` 0) or a meridian
+    (``kind`` 1) at ``pos`` (radians) and the bins along it."""
+    _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("pos", ctypes.c_double),
+                ("org", ctypes.c_double), ("inv_d", ctypes.c_double)]
+
+
+class CrossMapC(ctypes.Structure):
+    """``rwrt_cross_map``: the gates a ``rwrt_ray_cross`` call tests and the
+    maps it accumulates into (``need`` / ``wcol``: row columns, -1 for none)."""
+    _fields_ = [("ngate", ctypes.c_int32), ("nbin", ctypes.c_int32), ("nchan", ctypes.c_int32),
+                ("need", ctypes.c_int32), ("wcol", ctypes.c_int32), ("window_rows", ctypes.c_int32),
+                ("nwin", ctypes.c_int32), ("reserved", ctypes.c_int32), ("gate", CrossGateC * CROSS_MAXGATE)]
+
+
+assert ctypes.sizeof(CrossGateC) == 32 and ctypes.sizeof(CrossMapC) == 288
+
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
 NDIAG = 23     # RWRT_NDIAG: the planes of rwrt_bs_diag
 
@@ -130,6 +150,7 @@ def load():
     A = ctypes.POINTER(ArrivalMap)
     F = ctypes.POINTER(FluxMapC)
     T = ctypes.POINTER(TrackMapC)
+    X = ctypes.POINTER(CrossMapC)
     sig = {
         "rwrt_pack_fields": [G, _P, _P, _P],
         "rwrt_mercator_point": [G, _P, _I64, _P, _P, _P, _P],
@@ -150,6 +171,7 @@ def load():
         "rwrt_ray_arrival": [A, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_flux": [F, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_track": [T, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P],
+        "rwrt_ray_cross": [X, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_summary": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, R, _P, _P, _P],
         "rwrt_wn_map": [G, _P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_wn_fill": [_I32, _I32, _I32, _I32, _P, _P, _P],

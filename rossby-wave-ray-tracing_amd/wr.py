@@ -465,6 +465,57 @@ class WR:
             tmap.allreduce(group)
         return tmap
 
+    def ray_cross(self, spec, mode="hip", inte_method="rk45", by=None, group=None, root_method="numpy"):
+        """Initialise and integrate all rays like ``ray_run``, but test the
+        segment between every two consecutive output rows of a ray against the
+        gates of ``spec`` (cross.py) instead of delivering the history:
+        returns the ``cross.CrossMap`` -- per gate, direction and bin along the
+        gate the number of crossings, the sum of their times and, with
+        ``spec.weight``, of that column at the crossing, and per ray the
+        crossings and the first crossing time, arrays that reshape to
+        ``(ngate, 2, 3, nsource, nzwn)``; only row 0 of ``rlon .. rvg`` is
+        filled.
+
+        ``spec``: a ``cross.CrossSpec``.  ``by``: as in ``ray_density``.
+        ``mode='numpy'`` integrates on the GPU all the same, delivers the
+        history and applies ``cross.reference_cross`` on the host (small runs;
+        returns its dict).  With a process ``group`` every rank ends with the
+        sum over the ranks."""
+        import cross as X
+        import density as D
+        if by not in (None, "zwn", "root"):
+            raise ValueError("by must be None, 'zwn' or 'root'")
+        shape = (3, self.nsource, self.nzwn)
+        nray = 3 * self.nsource * self.nzwn
+        chan = None
+        if by is not None:
+            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
+            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
+            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
+        if mode == "numpy":
+            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
+            rows = np.full((nray, self.nt, 8), np.nan)
+            for c, h in enumerate((self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)):
+                rows[:, :, c] = h.reshape(self.nt, nray).T
+            return X.reference_cross(rows, chan, spec)
+        key = mode + "_rk45" if inte_method == "rk45" else mode
+        if key not in SUPPORTED:
+            self.core_ray_run(key)     # raises before any work
+        self.ray_initial(mode=mode, root_method=root_method)
+        import shard
+        world = shard.world_info(group)[1] if group is not None else 1
+        xmap = X.CrossMap(spec, nray, self.bs.engine().device, chan)
+
+        def column(col):
+            return None if col < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[col - 2][0]
+
+        # row 0 on every rank: the rank that integrates a ray carries it into row 1
+        xmap.start(self.rlon[0], self.rlat[0], column(spec.ncol), column(spec.wcol))
+        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=X.CrossSink(xmap))
+        if group is not None and shard.collective(world):
+            xmap.allreduce(group)
+        return xmap
+
     def ray_summary(self, regions=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but reduce every
         ray's rows to a path summary on the GPU (summary.py) instead of
