@@ -19,7 +19,8 @@ import numpy as np
 
 import _hip as H
 import density as D
-from launch_rows import RowSink, one_row, row_args
+from launch_rows import one_row, row_args
+from raymap import ChannelSink, DeviceMap, check_columns, counts_for
 
 INT32_MAX = 2 ** 31 - 1
 
@@ -41,8 +42,7 @@ class ArrivalSpec:
     window_rows: int = None
 
     def __post_init__(self):
-        if self.require is not None and self.require not in D.WEIGHT_COLUMNS:
-            raise ValueError(f"require must be None or one of {sorted(D.WEIGHT_COLUMNS)}")
+        check_columns(self, "require")
         self.bins                                        # (validates nx, ny, nchan, lat_range)
         if int(self.nt) != self.nt or not 1 <= self.nt <= INT32_MAX:
             raise ValueError("nt must be an integer of at least 1")
@@ -111,27 +111,23 @@ def reference_arrival(lon, lat, req, chan, spec, row0=0):
             "count": count}
 
 
-class ArrivalMap:
+class ArrivalMap(DeviceMap):
     """The device arrays of one map: ``first`` (int32, ``INT32_MAX``: none yet)
     and ``last`` (int32, -1: none yet), each ``[nchan, ny, nx]``, and ``count``
     (int64 ``[nwin, nchan, ny, nx]``, None without windows), initialised here
     and accumulated into by every ``add_rows`` / ``add_points`` call (time
-    chunks, shards) with min, max and add."""
+    chunks, shards) with min, max and add; ``allreduce`` combines the ranks'
+    maps the same way."""
+    REDUCE = (("first", "MIN"), ("last", "MAX"), ("count", "SUM"))
 
     def __init__(self, spec, device=None):
         import torch
-        H.require_gpu()
-        H.load()
-        self.spec = spec
-        self.device = torch.device(device or "cuda")
+        super().__init__(spec, device)
         self.first = torch.full(spec.shape, INT32_MAX, dtype=torch.int32, device=self.device)
         self.last = torch.full(spec.shape, -1, dtype=torch.int32, device=self.device)
         self.count = None
         if spec.window_rows is not None:
             self.count = torch.zeros(spec.count_shape, dtype=torch.int64, device=self.device)
-        self._c = spec.c_struct()
-
-    _chan = D.DensityMap._chan
 
     def add_rows(self, i0, i1, view, tails=None, slots=None, chan=None):
         """Reduce rows ``[i0, i1)`` of a launch (the arguments of
@@ -142,7 +138,7 @@ class ArrivalMap:
             raise ValueError(f"row {i1 - 1} is outside the {self.spec.nt} rows of the spec")
         nray, rows = row_args(i0, i1, view, tails, slots)
         chan = self._chan(chan, nray)
-        H.check(H.load().rwrt_ray_arrival(
+        H.check(self._lib.rwrt_ray_arrival(
             self._c, nray, int(i0), int(i1), *rows, H.dptr(chan, torch.int32), H.dptr(self.first, torch.int32),
             H.dptr(self.last, torch.int32), H.dptr(self.count, torch.int64), H.stream(self.device)))
 
@@ -156,21 +152,6 @@ class ArrivalMap:
                 raise ValueError(f"the map requires {self.spec.require!r}: pass req")
             cols[col] = req
         self.add_rows(0, 1, one_row(cols, self.device), chan=chan)
-
-    def allreduce(self, group=None):
-        """The maps of every rank of ``group`` combined -- MIN of ``first``, MAX
-        of ``last``, SUM of ``count`` -- and left on every rank."""
-        import torch.distributed as dist
-        from shard import _dev
-        for name, op in (("first", dist.ReduceOp.MIN), ("last", dist.ReduceOp.MAX), ("count", dist.ReduceOp.SUM)):
-            t = getattr(self, name)
-            if t is None:
-                continue
-            x = t.to(_dev(group))
-            dist.all_reduce(x, op=op, group=group)
-            if x is not t:
-                t.copy_(x)
-        return self
 
     def numpy(self):
         """``{'first', 'last', 'count'}`` on the host (waits for the pending
@@ -196,9 +177,6 @@ class ArrivalMap:
         rows = torch.as_tensor(np.nonzero((centre >= lat_s) & (centre <= lat_n))[0], device=self.device)
         return self.count.index_select(2, rows).sum(dim=2)
 
-    lon_edges = D.DensityMap.lon_edges
-    lat_edges = D.DensityMap.lat_edges
-
     def output(self, ncfile):
         """Write the map (dims ``window, chan, lat, lon``; bin centres in
         degrees).  ``first`` and ``last`` are int32; netCDF-3 has no 64-bit
@@ -207,32 +185,18 @@ class ArrivalMap:
         import ncio
         a = self.numpy()
         s = self.spec
-        le, la = self.lon_edges, self.lat_edges
-        dims = {"chan": s.nchan, "lat": s.ny, "lon": s.nx, "lat_edge": s.ny + 1, "lon_edge": s.nx + 1}
-        v = {"lon": (("lon",), 0.5 * (le[:-1] + le[1:]), "degrees"),
-             "lat": (("lat",), 0.5 * (la[:-1] + la[1:]), "degrees"),
-             "lon_edges": (("lon_edge",), le, "degrees"), "lat_edges": (("lat_edge",), la, "degrees"),
-             "first": (("chan", "lat", "lon"), a["first"], "output row (-1: none)"),
-             "last": (("chan", "lat", "lon"), a["last"], "output row (-1: none)")}
+        dims, v = self._grid_output()
+        v["first"] = (("chan", "lat", "lon"), a["first"], "output row (-1: none)")
+        v["last"] = (("chan", "lat", "lon"), a["last"], "output row (-1: none)")
         if a["count"] is not None:
-            count = a["count"] if str(ncfile).endswith(".npz") else a["count"].astype(np.float64)
             dims["window"] = s.nwin
             v["window_row"] = (("window",), np.arange(s.nwin, dtype=np.int32) * s.window_rows, "first output row")
-            v["count"] = (("window", "chan", "lat", "lon"), count, "ray points")
+            v["count"] = (("window", "chan", "lat", "lon"), counts_for(ncfile, a["count"]), "ray points")
         ncio.write(ncfile, dims, v)
 
 
-class ArrivalSink(RowSink):
+class ArrivalSink(ChannelSink):
     """A ``sink`` of ``RayEngine.integrate`` / ``integrate_rk4`` / ``resume``
     and of ``shard.run_sharded`` (``launch_rows.RowSink``) that reduces each
     launch's rows into ``map``.  ``chan``: each ray's channel (length nray;
     with ``run_sharded`` indexed by the shard's ``idx``; None: channel 0)."""
-
-    def __init__(self, map, chan=None):
-        super().__init__(map, None if chan is None else map._chan(chan, len(chan)))
-        self.map = map
-
-    chan = property(lambda self: self.per_ray)
-
-    def select(self, idx):
-        return None if self.per_ray is None else self.per_ray[idx]

@@ -24,8 +24,8 @@ from dataclasses import dataclass
 import numpy as np
 
 import _hip as H
-import density as D
-from launch_rows import RowSink, one_row, row_args
+from launch_rows import row_args
+from raymap import CarriedMap, ColumnSink, LatBand, RowColumns, check_columns, counts_for, valid_rows  # noqa: F401
 
 MAXGATE = H.CROSS_MAXGATE
 TWO_PI = 2.0 * math.pi
@@ -68,7 +68,7 @@ class Gate:
 
 
 @dataclass(frozen=True)
-class CrossSpec:
+class CrossSpec(LatBand, RowColumns):
     """Up to 8 ``gates`` with ``nbin`` bins along each: over longitude [0, 360)
     for a latitude circle, over ``lat_range`` (degrees) for a meridian, where
     a crossing outside the range is counted per ray and not in the map.
@@ -95,12 +95,8 @@ class CrossSpec:
             raise ValueError(f"gates must be 1..{MAXGATE} Gate objects")
         if self.nbin <= 0 or self.nchan <= 0:
             raise ValueError("nbin and nchan must be positive")
-        if not self.lat_range[1] > self.lat_range[0]:
-            raise ValueError("lat_range must be ascending")
-        for name in ("need", "weight"):
-            v = getattr(self, name)
-            if v is not None and v not in D.WEIGHT_COLUMNS:
-                raise ValueError(f"{name} must be None or one of {sorted(D.WEIGHT_COLUMNS)}")
+        self._check_lat_range()
+        check_columns(self, "need", "weight")
         if int(self.window_rows) != self.window_rows or self.window_rows < 0:
             raise ValueError("window_rows must be a non-negative integer")
         if self.window_rows > 0:
@@ -119,15 +115,6 @@ class CrossSpec:
             return 1
         return -(-(int(self.nt) - 1) // int(self.window_rows))
 
-    # pi * (deg / 180): +-90 give +-pi/2 exactly
-    @property
-    def lat0(self):
-        return math.pi * (float(self.lat_range[0]) / 180.0)
-
-    @property
-    def lat1(self):
-        return math.pi * (float(self.lat_range[1]) / 180.0)
-
     # the factors of the bins: computed here, once, in fp64, and passed to the
     # kernel (never recomputed on the device)
     @property
@@ -143,14 +130,6 @@ class CrossSpec:
         return (0.0, self.inv_dlon) if self.gates[g].kind == 0 else (self.lat0, self.inv_dlat)
 
     @property
-    def ncol(self):
-        return -1 if self.need is None else D.WEIGHT_COLUMNS[self.need]
-
-    @property
-    def wcol(self):
-        return -1 if self.weight is None else D.WEIGHT_COLUMNS[self.weight]
-
-    @property
     def shape(self):
         return (self.nwin, self.ngate, 2, self.nchan, self.nbin)
 
@@ -160,16 +139,6 @@ class CrossSpec:
             org, inv_d = self.axis(g)
             c.gate[g] = H.CrossGateC(gate.kind, 0, gate.pos, org, inv_d)
         return c
-
-
-def valid_rows(rows, spec):
-    """``[nray, nt]`` bool: lon and lat finite and, with ``need`` / ``weight``,
-    those columns finite too."""
-    ok = np.isfinite(rows[..., 0]) & np.isfinite(rows[..., 1])
-    for col in (spec.ncol, spec.wcol):
-        if col >= 0:
-            ok &= np.isfinite(rows[..., col])
-    return ok
 
 
 def sides(rows, gate):
@@ -309,26 +278,20 @@ def reference_cross(rows, chan, spec):
     return {"cnt": cnt, "tsum": tsum, "wsum": wsum, "dropped": dropped, "ncross": ncross, "tfirst": tfirst}
 
 
-class CrossMap:
+class CrossMap(CarriedMap):
     """The device arrays of one set of gates over ``nray`` rays: ``cnt``
     (int64), ``tsum`` and ``wsum`` (fp64; ``wsum`` None without a weight), each
     ``[nwin, ngate, 2, nchan, nbin]``, ``dropped`` (int64 ``[1]``), ``ncross``
     (int32) and ``tfirst`` (fp64, NaN for none), each ``[ngate, 2, nray]``,
     initialised here and accumulated into by every ``add_rows`` call (time
-    chunks, shards); and ``prev`` (fp64 ``[3, nray]``: lon, lat, weight
-    value), each ray's carried previous row, NaN for none.  ``prev`` is a
-    running state, not a sum: a ray's rows must arrive once, in order, each
-    call starting at the row the previous one ended with (``start`` is row 0).
-    ``chan``: each ray's channel, indexed by the ray's column (None: channel
-    0); a ray with a channel outside ``[0, nchan)`` contributes nothing."""
+    chunks, shards).  The carried rows (``prev``, ``start``, ``restart``) and
+    ``chan`` are ``raymap.CarriedMap``'s; a ray with a channel outside
+    ``[0, nchan)`` contributes nothing."""
+    REDUCE = (("cnt", "SUM"), ("tsum", "SUM"), ("wsum", "SUM"), ("dropped", "SUM"), ("ncross", "SUM"))
 
     def __init__(self, spec, nray, device=None, chan=None):
         import torch
-        H.require_gpu()
-        H.load()
-        self.spec = spec
-        self.nray = int(nray)
-        self.device = torch.device(device or "cuda")
+        super().__init__(spec, nray, device, chan)
         f64 = dict(dtype=torch.float64, device=self.device)
         self.cnt = torch.zeros(spec.shape, dtype=torch.int64, device=self.device)
         self.tsum = torch.zeros(spec.shape, **f64)
@@ -336,30 +299,6 @@ class CrossMap:
         self.dropped = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.ncross = torch.zeros((spec.ngate, 2, self.nray), dtype=torch.int32, device=self.device)
         self.tfirst = torch.full((spec.ngate, 2, self.nray), math.nan, **f64)
-        self.prev = torch.full((3, self.nray), math.nan, **f64)
-        self.chan = None
-        if chan is not None:
-            self.chan = torch.as_tensor(chan, device=self.device).to(torch.int32).contiguous()
-            if self.chan.numel() != self.nray:
-                raise ValueError(f"chan has {self.chan.numel()} entries for {self.nray} rays")
-        self._c = spec.c_struct()
-        self._lib = H.load()
-
-    def restart(self):
-        """Forget every ray's carried row (the maps and the per-ray arrays stay)."""
-        self.prev.fill_(math.nan)
-        return self
-
-    def _ray(self, ray, n):
-        import torch
-        if ray is None:
-            if n != self.nray:
-                raise ValueError(f"{n} rays for {self.nray} columns: pass ray (each ray's column)")
-            return None
-        ray = torch.as_tensor(ray, device=self.device).to(torch.int64).contiguous()
-        if ray.numel() != n:
-            raise ValueError(f"ray has {ray.numel()} entries for {n} rays")
-        return ray
 
     def add_rows(self, i0, i1, view, tails=None, slots=None, ray=None):
         """Find the crossings of the segments that end on rows ``[i0, i1)`` of
@@ -377,20 +316,6 @@ class CrossMap:
             H.dptr(self.wsum), H.dptr(self.dropped, torch.int64), H.dptr(self.ncross, torch.int32),
             H.dptr(self.tfirst, torch.float64), H.stream(self.device)))
 
-    def start(self, lon, lat, need=None, v=None, ray=None):
-        """Row 0, the initial rays (radians), which sinks never receive: the
-        same entry point on a ``[n, 1, 8]`` row tensor; it crosses nothing and
-        sets the carried rows.  ``need`` / ``v``: the values of the ``need``
-        and ``weight`` columns (required when the spec names them)."""
-        cols = {0: lon, 1: lat}
-        for name, col, val in (("need", self.spec.ncol, need), ("weight", self.spec.wcol, v)):
-            if col >= 0:
-                if val is None:
-                    raise ValueError(f"the map's {name} column is {getattr(self.spec, name)!r}: pass its values")
-                cols[col] = val
-        self.add_rows(0, 1, one_row(cols, self.device), ray=ray)
-        return self
-
     def allreduce(self, group=None):
         """SUM of the maps, of ``dropped`` and of ``ncross`` over the ranks of
         ``group``, left on every rank; ``tfirst`` of a ray is the value of the
@@ -399,13 +324,7 @@ class CrossMap:
         import torch
         import torch.distributed as dist
         from shard import _dev
-        for t in (self.cnt, self.tsum, self.wsum, self.dropped, self.ncross):
-            if t is None:
-                continue
-            x = t.to(_dev(group))
-            dist.all_reduce(x, op=dist.ReduceOp.SUM, group=group)
-            if x is not t:
-                t.copy_(x)
+        super().allreduce(group)
         x = torch.nan_to_num(self.tfirst, nan=math.inf).to(_dev(group))
         dist.all_reduce(x, op=dist.ReduceOp.MIN, group=group)
         x = x.to(self.device)
@@ -472,8 +391,6 @@ class CrossMap:
         import ncio
         a = self.numpy()
         s = self.spec
-        npz = str(ncfile).endswith(".npz")
-        cnt = a["cnt"] if npz else a["cnt"].astype(np.float64)
         edges = np.stack([self.bin_edges(g) for g in range(s.ngate)])
         dims = {"win": s.nwin, "gate": s.ngate, "dir": 2, "chan": s.nchan, "bin": s.nbin, "bin_edge": s.nbin + 1,
                 "ray": self.nray, "one": 1}
@@ -482,7 +399,7 @@ class CrossMap:
              "gate_pos": (("gate",), np.array([float(g.deg) for g in s.gates]), "degrees"),
              "bin_centres": (("gate", "bin"), 0.5 * (edges[:, :-1] + edges[:, 1:]), "degrees"),
              "bin_edges": (("gate", "bin_edge"), edges, "degrees"),
-             "cnt": (full, cnt, "crossings"), "tsum": (full, a["tsum"], "rows"),
+             "cnt": (full, counts_for(ncfile, a["cnt"]), "crossings"), "tsum": (full, a["tsum"], "rows"),
              "dropped": (("one",), np.array([float(a["dropped"])]), "segments"),
              "ncross": (per_ray, a["ncross"], "crossings"),
              "tfirst": (per_ray, a["tfirst"], "rows")}
@@ -491,19 +408,10 @@ class CrossMap:
         ncio.write(ncfile, dims, v)
 
 
-class CrossSink(RowSink):
+class CrossSink(ColumnSink):
     """A ``sink`` of ``RayEngine.integrate`` / ``integrate_rk4`` / ``resume``
     and of ``shard.run_sharded`` (``launch_rows.RowSink``) that tests each
     launch's segments against the gates of ``map``.  ``ray``: the column of
     each ray of the integration (None: ray j is column j); the sharded form's
     ``idx`` and ``take(idx)`` select from it, or are the columns themselves.
     Channels are the map's (``CrossMap.chan``), indexed by column."""
-
-    def __init__(self, map, ray=None):
-        super().__init__(map, ray if ray is None else map._ray(ray, len(ray)))
-        self.map = map
-
-    ray = property(lambda self: self.per_ray)
-
-    def select(self, idx):
-        return idx if self.per_ray is None else self.per_ray[idx]

@@ -24,6 +24,7 @@
 #include "rwrt.h"
 #include "abi_host.h"
 #include "arrival_rows.h"
+#include "map_host.h"
 
 #ifndef RWRT_ARRIVAL_SKIP
 #define RWRT_ARRIVAL_SKIP 1
@@ -79,17 +80,10 @@ extern "C" rwrt_status rwrt_ray_arrival(const rwrt_arrival_map* m, int64_t nray,
   // (every check before the first HIP call)
   if (!m) return fail(RWRT_ERR_ARG, "rwrt_ray_arrival: map is NULL%s", "");
   const rwrt_density_map& b = m->bins;
-  if (b.nx <= 0 || b.ny <= 0 || b.nchan <= 0)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_arrival: nx, ny and nchan must be positive%s", "");
-  if ((int64_t)b.nx * b.ny >= (1LL << 31) || (int64_t)b.nx * b.ny * b.nchan >= (1LL << 31))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_arrival: nchan*ny*nx must be below 2^31%s", "");
-  if (!(b.wcol == -1 || (b.wcol >= 2 && b.wcol <= 6)))
+  if (const rwrt_status st = check_map_shape("rwrt_ray_arrival", b.nx, b.ny, b.nchan)) return st;
+  if (!map_column_ok(b.wcol))
     return fail(RWRT_ERR_ARG, "rwrt_ray_arrival: wcol must be -1 or 2..6 (k l amp ug vg)%s", "");
-  if (!(b.inv_dlon > 0.0) || !std::isfinite(b.inv_dlon))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_arrival: inv_dlon must be finite and positive%s", "");
-  if (!(b.inv_dlat > 0.0) || !std::isfinite(b.inv_dlat))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_arrival: inv_dlat must be finite and positive%s", "");
-  if (!std::isfinite(b.lat0)) return fail(RWRT_ERR_ARG, "rwrt_ray_arrival: lat0 must be finite%s", "");
+  if (const rwrt_status st = check_map_axes("rwrt_ray_arrival", b.inv_dlon, b.inv_dlat, b.lat0)) return st;
   if (const rwrt_status st = check_launch_rows("rwrt_ray_arrival", nray, it_begin, it_end, d_rows, d_row_slot,
                                                d_tail_from, d_tail_row))
     return st;
@@ -108,9 +102,7 @@ extern "C" rwrt_status rwrt_ray_arrival(const rwrt_arrival_map* m, int64_t nray,
       return fail(RWRT_ERR_ARG, "rwrt_ray_arrival: it_end is past nwin*window_rows, the last row of d_count%s", "");
   }
   if (nray == 0) return RWRT_OK;
-  const unsigned blocks = (unsigned)((nray + 255) / 256);
-  hipLaunchKernelGGL(ray_arrival_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *m, nray, it_begin,
-                     it_end, d_rows, d_row_slot, d_tail_from, d_tail_row, d_chan, d_first, d_last,
-                     reinterpret_cast<unsigned long long*>(d_count));
-  return check_launch("ray_arrival_kernel");
+  return launch_per_ray("ray_arrival_kernel", ray_arrival_kernel, nray, stream, *m, nray, it_begin, it_end, d_rows,
+                        d_row_slot, d_tail_from, d_tail_row, d_chan, d_first, d_last,
+                        reinterpret_cast<unsigned long long*>(d_count));
 }

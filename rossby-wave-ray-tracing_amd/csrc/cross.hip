@@ -24,6 +24,7 @@
 #include "rwrt.h"
 #include "abi_host.h"
 #include "cross_lines.h"
+#include "map_host.h"
 
 namespace rwrt {
 namespace {
@@ -89,20 +90,6 @@ ray_cross_kernel(const rwrt_cross_map m, int64_t nray, int32_t it_begin, int32_t
   }
 }
 
-bool cross_column_ok(int32_t col) { return col == -1 || (col >= 2 && col <= 6); }
-
-template <int NG>
-void launch_cross(unsigned blocks, hipStream_t stream, const rwrt_cross_map& m, int64_t nray, int32_t it_begin,
-                  int32_t it_end, const double* d_rows, const int32_t* d_row_slot, const int32_t* d_tail_from,
-                  const double* d_tail_row, const int64_t* d_ray, int64_t nacc_cols, const int32_t* d_chan,
-                  double* d_prev, int64_t* d_cnt, double* d_tsum, double* d_wsum, int64_t* d_dropped,
-                  int32_t* d_ncross, double* d_tfirst) {
-  hipLaunchKernelGGL(ray_cross_kernel<NG>, dim3(blocks), dim3(256), 0, stream, m, nray, it_begin, it_end, d_rows,
-                     d_row_slot, d_tail_from, d_tail_row, d_ray, nacc_cols, d_chan, d_prev,
-                     reinterpret_cast<unsigned long long*>(d_cnt), d_tsum, d_wsum,
-                     reinterpret_cast<unsigned long long*>(d_dropped), d_ncross, d_tfirst);
-}
-
 }  // namespace
 }  // namespace rwrt
 
@@ -144,8 +131,8 @@ extern "C" rwrt_status rwrt_ray_cross(const rwrt_cross_map* m, int64_t nray, int
     if (q.kind == 1 && !(q.pos >= 0.0 && q.pos < kCrossTwoPi))
       return fail(RWRT_ERR_ARG, "rwrt_ray_cross: gate %s: pos of a meridian must lie in [0, 2 pi)", kGate[g]);
   }
-  if (!cross_column_ok(m->need)) return fail(RWRT_ERR_ARG, "rwrt_ray_cross: need must be -1 or a column 2..6%s", "");
-  if (!cross_column_ok(m->wcol)) return fail(RWRT_ERR_ARG, "rwrt_ray_cross: wcol must be -1 or a column 2..6%s", "");
+  if (!map_column_ok(m->need)) return fail(RWRT_ERR_ARG, "rwrt_ray_cross: need must be -1 or a column 2..6%s", "");
+  if (!map_column_ok(m->wcol)) return fail(RWRT_ERR_ARG, "rwrt_ray_cross: wcol must be -1 or a column 2..6%s", "");
   if (const rwrt_status st = check_launch_rows("rwrt_ray_cross", nray, it_begin, it_end, d_rows, d_row_slot,
                                                d_tail_from, d_tail_row))
     return st;
@@ -163,13 +150,12 @@ extern "C" rwrt_status rwrt_ray_cross(const rwrt_cross_map* m, int64_t nray, int
   if (!d_ncross != !d_tfirst)
     return fail(RWRT_ERR_ARG, "rwrt_ray_cross: the per-ray arrays need both d_ncross and d_tfirst%s", "");
   if (nray == 0) return RWRT_OK;
-  const unsigned blocks = (unsigned)((nray + 255) / 256);
-  const hipStream_t st = (hipStream_t)stream;
-#define RWRT_CROSS_CASE(NG)                                                                                       \
-  case NG:                                                                                                        \
-    launch_cross<NG>(blocks, st, *m, nray, it_begin, it_end, d_rows, d_row_slot, d_tail_from, d_tail_row, d_ray, \
-                     nacc_cols, d_chan, d_prev, d_cnt, d_tsum, d_wsum, d_dropped, d_ncross, d_tfirst);           \
-    break;
+#define RWRT_CROSS_CASE(NG)                                                                                      \
+  case NG:                                                                                                       \
+    return launch_per_ray("ray_cross_kernel", ray_cross_kernel<NG>, nray, stream, *m, nray, it_begin, it_end,    \
+                          d_rows, d_row_slot, d_tail_from, d_tail_row, d_ray, nacc_cols, d_chan, d_prev,         \
+                          reinterpret_cast<unsigned long long*>(d_cnt), d_tsum, d_wsum,                          \
+                          reinterpret_cast<unsigned long long*>(d_dropped), d_ncross, d_tfirst);
   switch (m->ngate) {
     RWRT_CROSS_CASE(1)
     RWRT_CROSS_CASE(2)
@@ -181,5 +167,5 @@ extern "C" rwrt_status rwrt_ray_cross(const rwrt_cross_map* m, int64_t nray, int
     RWRT_CROSS_CASE(8)
   }
 #undef RWRT_CROSS_CASE
-  return check_launch("ray_cross_kernel");
+  return RWRT_OK;   // (not reached: ngate was checked above)
 }

@@ -21,6 +21,7 @@
 #include "abi_host.h"
 #include "density_bins.h"
 #include "launch_rows.h"
+#include "map_host.h"
 
 namespace rwrt {
 namespace {
@@ -96,26 +97,17 @@ extern "C" rwrt_status rwrt_ray_density(const rwrt_density_map* m, int64_t nray,
                                         const int32_t* d_chan, int64_t* d_count, double* d_wsum, void* stream) {
   // (every check before the first HIP call)
   if (!m) return fail(RWRT_ERR_ARG, "rwrt_ray_density: map is NULL%s", "");
-  if (m->nx <= 0 || m->ny <= 0 || m->nchan <= 0)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_density: nx, ny and nchan must be positive%s", "");
-  if ((int64_t)m->nx * m->ny >= (1LL << 31) || (int64_t)m->nx * m->ny * m->nchan >= (1LL << 31))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_density: nchan*ny*nx must be below 2^31%s", "");
-  if (!(m->wcol == -1 || (m->wcol >= 2 && m->wcol <= 6)))
+  if (const rwrt_status st = check_map_shape("rwrt_ray_density", m->nx, m->ny, m->nchan)) return st;
+  if (!map_column_ok(m->wcol))
     return fail(RWRT_ERR_ARG, "rwrt_ray_density: wcol must be -1 or 2..6 (k l amp ug vg)%s", "");
-  if (!(m->inv_dlon > 0.0) || !std::isfinite(m->inv_dlon))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_density: inv_dlon must be finite and positive%s", "");
-  if (!(m->inv_dlat > 0.0) || !std::isfinite(m->inv_dlat))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_density: inv_dlat must be finite and positive%s", "");
-  if (!std::isfinite(m->lat0)) return fail(RWRT_ERR_ARG, "rwrt_ray_density: lat0 must be finite%s", "");
+  if (const rwrt_status st = check_map_axes("rwrt_ray_density", m->inv_dlon, m->inv_dlat, m->lat0)) return st;
   if (m->wcol >= 0 && !d_wsum) return fail(RWRT_ERR_ARG, "rwrt_ray_density: wcol >= 0 needs d_wsum%s", "");
   if (const rwrt_status st = check_launch_rows("rwrt_ray_density", nray, it_begin, it_end, d_rows, d_row_slot,
                                                d_tail_from, d_tail_row))
     return st;
   if (!d_count) return fail(RWRT_ERR_ARG, "rwrt_ray_density: d_count is NULL%s", "");
   if (nray == 0) return RWRT_OK;
-  const unsigned blocks = (unsigned)((nray + 255) / 256);
-  hipLaunchKernelGGL(ray_density_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *m, nray, it_begin,
-                     it_end, d_rows, d_row_slot, d_tail_from, d_tail_row, d_chan,
-                     reinterpret_cast<unsigned long long*>(d_count), d_wsum);
-  return check_launch("ray_density_kernel");
+  return launch_per_ray("ray_density_kernel", ray_density_kernel, nray, stream, *m, nray, it_begin, it_end, d_rows,
+                        d_row_slot, d_tail_from, d_tail_row, d_chan, reinterpret_cast<unsigned long long*>(d_count),
+                        d_wsum);
 }

@@ -30,6 +30,7 @@
 #include "rwrt.h"
 #include "abi_host.h"
 #include "flux_rows.h"
+#include "map_host.h"
 
 namespace rwrt {
 namespace {
@@ -99,20 +100,12 @@ extern "C" rwrt_status rwrt_ray_flux(const rwrt_flux_map* m, int64_t nray, int32
                                      const int32_t* d_chan, int64_t* d_cnt, double* d_sum, void* stream) {
   // (every check before the first HIP call)
   if (!m) return fail(RWRT_ERR_ARG, "rwrt_ray_flux: map is NULL%s", "");
-  if (m->nx <= 0 || m->ny <= 0 || m->nchan <= 0)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_flux: nx, ny and nchan must be positive%s", "");
-  if ((int64_t)m->nx * m->ny >= (1LL << 31) || (int64_t)m->nx * m->ny * m->nchan >= (1LL << 31))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_flux: nchan*ny*nx must be below 2^31%s", "");
+  if (const rwrt_status st = check_map_shape("rwrt_ray_flux", m->nx, m->ny, m->nchan)) return st;
   if (m->mode < 0 || m->mode >= 4)
     return fail(RWRT_ERR_ARG, "rwrt_ray_flux: mode has bits other than 0 (unit vectors) and 1 (unwrapped)%s", "");
-  if (!(m->inv_dlon > 0.0) || !std::isfinite(m->inv_dlon))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_flux: inv_dlon must be finite and positive%s", "");
-  if (!(m->inv_dlat > 0.0) || !std::isfinite(m->inv_dlat))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_flux: inv_dlat must be finite and positive%s", "");
-  if (!std::isfinite(m->lat0)) return fail(RWRT_ERR_ARG, "rwrt_ray_flux: lat0 must be finite%s", "");
-  if (!std::isfinite(m->lon0)) return fail(RWRT_ERR_ARG, "rwrt_ray_flux: lon0 must be finite%s", "");
-  if (!(m->mode & kFluxUnwrapped) && m->lon0 != 0.0)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_flux: lon0 must be 0 for a wrapped longitude (mode bit 1 clear)%s", "");
+  if (const rwrt_status st = check_map_axes("rwrt_ray_flux", m->inv_dlon, m->inv_dlat, m->lat0, m->lon0,
+                                            m->mode & kFluxUnwrapped))
+    return st;
   if (!(m->s2_min >= 0.0)) return fail(RWRT_ERR_ARG, "rwrt_ray_flux: s2_min must not be NaN or negative%s", "");
   if (!(m->s2_max >= m->s2_min))
     return fail(RWRT_ERR_ARG, "rwrt_ray_flux: s2_max must not be NaN or below s2_min%s", "");
@@ -123,9 +116,6 @@ extern "C" rwrt_status rwrt_ray_flux(const rwrt_flux_map* m, int64_t nray, int32
   if (!d_cnt) return fail(RWRT_ERR_ARG, "rwrt_ray_flux: d_cnt is NULL%s", "");
   if (!d_sum) return fail(RWRT_ERR_ARG, "rwrt_ray_flux: d_sum is NULL%s", "");
   if (nray == 0) return RWRT_OK;
-  const unsigned blocks = (unsigned)((nray + 255) / 256);
-  hipLaunchKernelGGL(ray_flux_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *m, nray, it_begin, it_end,
-                     d_rows, d_row_slot, d_tail_from, d_tail_row, d_chan,
-                     reinterpret_cast<unsigned long long*>(d_cnt), d_sum);
-  return check_launch("ray_flux_kernel");
+  return launch_per_ray("ray_flux_kernel", ray_flux_kernel, nray, stream, *m, nray, it_begin, it_end, d_rows,
+                        d_row_slot, d_tail_from, d_tail_row, d_chan, reinterpret_cast<unsigned long long*>(d_cnt), d_sum);
 }

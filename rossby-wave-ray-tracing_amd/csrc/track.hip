@@ -21,6 +21,7 @@
 
 #include "rwrt.h"
 #include "abi_host.h"
+#include "map_host.h"
 #include "track_cells.h"
 
 // -DRWRT_TRACK_COUNT_FLUSHES=1 (make variant NAME=trackcount DEFS=...): an A/B
@@ -85,8 +86,6 @@ ray_track_kernel(const rwrt_track_map m, int64_t nray, int32_t it_begin, int32_t
   }
 }
 
-bool track_column_ok(int32_t col) { return col == -1 || (col >= 2 && col <= 6); }
-
 }  // namespace
 }  // namespace rwrt
 
@@ -99,23 +98,15 @@ extern "C" rwrt_status rwrt_ray_track(const rwrt_track_map* m, int64_t nray, int
                                       double* d_time, double* d_wsum, int64_t* d_dropped, void* stream) {
   // (every check before the first HIP call)
   if (!m) return fail(RWRT_ERR_ARG, "rwrt_ray_track: map is NULL%s", "");
-  if (m->nx <= 0 || m->ny <= 0 || m->nchan <= 0)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_track: nx, ny and nchan must be positive%s", "");
-  if ((int64_t)m->nx * m->ny >= (1LL << 31) || (int64_t)m->nx * m->ny * m->nchan >= (1LL << 31))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_track: nchan*ny*nx must be below 2^31%s", "");
+  if (const rwrt_status st = check_map_shape("rwrt_ray_track", m->nx, m->ny, m->nchan)) return st;
   if (m->mode != 0 && m->mode != kTrackUnwrapped)
     return fail(RWRT_ERR_ARG, "rwrt_ray_track: mode has bits other than 1 (unwrapped)%s", "");
   if (m->max_cells < 1) return fail(RWRT_ERR_ARG, "rwrt_ray_track: max_cells must be at least 1%s", "");
-  if (!track_column_ok(m->need)) return fail(RWRT_ERR_ARG, "rwrt_ray_track: need must be -1 or a column 2..6%s", "");
-  if (!track_column_ok(m->wcol)) return fail(RWRT_ERR_ARG, "rwrt_ray_track: wcol must be -1 or a column 2..6%s", "");
-  if (!(m->inv_dlon > 0.0) || !std::isfinite(m->inv_dlon))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_track: inv_dlon must be finite and positive%s", "");
-  if (!(m->inv_dlat > 0.0) || !std::isfinite(m->inv_dlat))
-    return fail(RWRT_ERR_ARG, "rwrt_ray_track: inv_dlat must be finite and positive%s", "");
-  if (!std::isfinite(m->lat0)) return fail(RWRT_ERR_ARG, "rwrt_ray_track: lat0 must be finite%s", "");
-  if (!std::isfinite(m->lon0)) return fail(RWRT_ERR_ARG, "rwrt_ray_track: lon0 must be finite%s", "");
-  if (!(m->mode & kTrackUnwrapped) && m->lon0 != 0.0)
-    return fail(RWRT_ERR_ARG, "rwrt_ray_track: lon0 must be 0 for a wrapped longitude (mode bit 1 clear)%s", "");
+  if (!map_column_ok(m->need)) return fail(RWRT_ERR_ARG, "rwrt_ray_track: need must be -1 or a column 2..6%s", "");
+  if (!map_column_ok(m->wcol)) return fail(RWRT_ERR_ARG, "rwrt_ray_track: wcol must be -1 or a column 2..6%s", "");
+  if (const rwrt_status st = check_map_axes("rwrt_ray_track", m->inv_dlon, m->inv_dlat, m->lat0, m->lon0,
+                                            m->mode & kTrackUnwrapped))
+    return st;
   if (const rwrt_status st = check_launch_rows("rwrt_ray_track", nray, it_begin, it_end, d_rows, d_row_slot,
                                                d_tail_from, d_tail_row))
     return st;
@@ -129,10 +120,8 @@ extern "C" rwrt_status rwrt_ray_track(const rwrt_track_map* m, int64_t nray, int
   if (m->wcol < 0 && d_wsum) return fail(RWRT_ERR_ARG, "rwrt_ray_track: d_wsum needs a weight column (wcol)%s", "");
   if (!d_dropped) return fail(RWRT_ERR_ARG, "rwrt_ray_track: d_dropped is NULL%s", "");
   if (nray == 0) return RWRT_OK;
-  const unsigned blocks = (unsigned)((nray + 255) / 256);
-  hipLaunchKernelGGL(ray_track_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *m, nray, it_begin, it_end,
-                     d_rows, d_row_slot, d_tail_from, d_tail_row, d_ray, nacc_cols, d_chan, d_prev,
-                     reinterpret_cast<unsigned long long*>(d_cnt), d_time, d_wsum,
-                     reinterpret_cast<unsigned long long*>(d_dropped));
-  return check_launch("ray_track_kernel");
+  return launch_per_ray("ray_track_kernel", ray_track_kernel, nray, stream, *m, nray, it_begin, it_end, d_rows,
+                        d_row_slot, d_tail_from, d_tail_row, d_ray, nacc_cols, d_chan, d_prev,
+                        reinterpret_cast<unsigned long long*>(d_cnt), d_time, d_wsum,
+                        reinterpret_cast<unsigned long long*>(d_dropped));
 }

@@ -28,14 +28,15 @@ import numpy as np
 
 import _hip as H
 import density as D
-from launch_rows import RowSink, one_row, row_args
+from launch_rows import one_row, row_args
+from raymap import ChannelSink, DeviceMap, GridSpec, counts_for, fold_arrays  # noqa: F401
 
 VECTORS = ("velocity", "unit")
 MODE_UNIT, MODE_UNWRAPPED = 1, 2
 
 
 @dataclass(frozen=True)
-class FluxSpec:
+class FluxSpec(GridSpec):
     """``nx`` bins over the longitude axis, ``ny`` over ``lat_range`` (degrees,
     upper edge excluded), ``nchan`` maps.  ``lon_range=None``: wrapped
     longitude, [0, 360), binned exactly like a ``density.DensitySpec``;
@@ -54,16 +55,8 @@ class FluxSpec:
     wn_max: float = math.inf
 
     def __post_init__(self):
-        if self.nx <= 0 or self.ny <= 0 or self.nchan <= 0:
-            raise ValueError("nx, ny and nchan must be positive")
-        if self.nx * self.ny * self.nchan >= 2 ** 31:
-            raise ValueError("nchan*ny*nx must be below 2^31")
-        if not self.lat_range[1] > self.lat_range[0]:
-            raise ValueError("lat_range must be ascending")
-        if self.lon_range is not None:
-            a, b = (float(v) for v in self.lon_range)
-            if not (math.isfinite(a) and math.isfinite(b) and b > a):
-                raise ValueError("lon_range must be None or finite and ascending")
+        self._check_shape()
+        self._check_ranges()
         if self.vector not in VECTORS:
             raise ValueError(f"vector must be one of {VECTORS}")
         smin, smax = (float(v) for v in self.speed_range)
@@ -72,37 +65,8 @@ class FluxSpec:
         if not float(self.wn_max) >= 0.0:
             raise ValueError("wn_max must not be negative")
 
-    # pi * (deg / 180): +-90 give +-pi/2 exactly
-    @property
-    def lat0(self):
-        return math.pi * (float(self.lat_range[0]) / 180.0)
-
-    @property
-    def lat1(self):
-        return math.pi * (float(self.lat_range[1]) / 180.0)
-
-    @property
-    def unwrapped(self):
-        return self.lon_range is not None
-
-    @property
-    def lon0(self):
-        return math.pi * (float(self.lon_range[0]) / 180.0) if self.unwrapped else 0.0
-
-    @property
-    def lon1(self):
-        return math.pi * (float(self.lon_range[1]) / 180.0) if self.unwrapped else 2 * math.pi
-
-    # the factors of the index arithmetic and the squared speed bounds: computed
-    # here, once, in fp64, and passed to the kernel (never recomputed on the device)
-    @property
-    def inv_dlon(self):
-        return self.nx / (self.lon1 - self.lon0)
-
-    @property
-    def inv_dlat(self):
-        return self.ny / (self.lat1 - self.lat0)
-
+    # the squared speed bounds: computed here, once, in fp64, like the grid's
+    # factors (raymap.GridSpec), and passed to the kernel
     @property
     def s2_min(self):
         return float(self.speed_range[0]) * float(self.speed_range[0])
@@ -118,20 +82,6 @@ class FluxSpec:
     @property
     def mode(self):
         return (MODE_UNIT if self.unit else 0) | (MODE_UNWRAPPED if self.unwrapped else 0)
-
-    @property
-    def shape(self):
-        return (self.nchan, self.ny, self.nx)
-
-    @property
-    def circles(self):
-        """The whole circles of an unwrapped window that starts on a multiple
-        of 360 degrees; None for any other axis."""
-        if not self.unwrapped:
-            return None
-        a, b = (float(v) for v in self.lon_range)
-        n = (b - a) / 360.0
-        return int(n) if a % 360.0 == 0.0 and n == int(n) else None
 
     def c_struct(self):
         return H.FluxMapC(self.nx, self.ny, self.nchan, self.mode, self.lon0, self.inv_dlon, self.lat0,
@@ -207,47 +157,28 @@ def reference_flux(lon, lat, k, l, ug, vg, chan, spec, row0=0):
             "sum": total.reshape(spec.shape + (3,))}
 
 
-def fold_arrays(spec, *arrays):
-    """``(spec', arrays')``: an unwrapped map of ``spec.circles`` whole circles
-    summed onto [0, 360) -- ``spec'`` the wrapped spec of ``nx / circles``
-    bins; each array is ``[nchan, ny, nx, ...]`` (NumPy or torch)."""
-    from dataclasses import replace
-    nc = spec.circles
-    if nc is None:
-        raise ValueError("fold() needs an unwrapped window of whole circles that starts on a multiple of 360 degrees")
-    if spec.nx % nc:
-        raise ValueError(f"fold() needs nx divisible by the {nc} circles of the window, got nx = {spec.nx}")
-    per = spec.nx // nc
-    out = [a.reshape(tuple(a.shape[:2]) + (nc, per) + tuple(a.shape[3:])).sum(2) for a in arrays]
-    return replace(spec, nx=per, lon_range=None), out
-
-
-class FluxMap:
+class FluxMap(DeviceMap):
     """The device arrays of one map: ``cnt`` (int64 ``[nchan, ny, nx, 2]``:
     count, rowsum) and ``sum`` (fp64 ``[nchan, ny, nx, 3]``: fx, fy, fs),
     zeroed here and accumulated into by every ``add_rows`` / ``add_points``
     call (time chunks, shards).  A bin's accumulators are interleaved (the
     layout of ``rwrt_ray_flux``); ``count``, ``rowsum``, ``fx``, ``fy``, ``fs``
-    are views.  ``selected``: set by ``WR.ray_flux(through=...)``."""
+    are views; ``allreduce`` sums both tensors over the ranks.  ``selected``:
+    set by ``WR.ray_flux(through=...)``."""
+    REDUCE = (("cnt", "SUM"), ("sum", "SUM"))
 
     def __init__(self, spec, device=None):
         import torch
-        H.require_gpu()
-        H.load()
-        self.spec = spec
-        self.device = torch.device(device or "cuda")
+        super().__init__(spec, device)
         self.cnt = torch.zeros(spec.shape + (2,), dtype=torch.int64, device=self.device)
         self.sum = torch.zeros(spec.shape + (3,), dtype=torch.float64, device=self.device)
         self.selected = None
-        self._c = spec.c_struct()
 
     count = property(lambda self: self.cnt[..., 0])
     rowsum = property(lambda self: self.cnt[..., 1])
     fx = property(lambda self: self.sum[..., 0])
     fy = property(lambda self: self.sum[..., 1])
     fs = property(lambda self: self.sum[..., 2])
-
-    _chan = D.DensityMap._chan
 
     def add_rows(self, i0, i1, view, tails=None, slots=None, chan=None):
         """Reduce rows ``[i0, i1)`` of a launch (the arguments of
@@ -256,7 +187,7 @@ class FluxMap:
         import torch
         nray, rows = row_args(i0, i1, view, tails, slots)
         chan = self._chan(chan, nray)
-        H.check(H.load().rwrt_ray_flux(
+        H.check(self._lib.rwrt_ray_flux(
             self._c, nray, int(i0), int(i1), *rows, H.dptr(chan, torch.int32), H.dptr(self.cnt, torch.int64),
             H.dptr(self.sum, torch.float64), H.stream(self.device)))
 
@@ -265,33 +196,12 @@ class FluxMap:
         sinks never receive."""
         self.add_rows(0, 1, one_row({0: lon, 1: lat, 2: k, 3: l, 5: ug, 6: vg}, self.device), chan=chan)
 
-    def allreduce(self, group=None):
-        """SUM of the maps of every rank of ``group`` (both tensors), left on
-        every rank."""
-        import torch.distributed as dist
-        from shard import _dev
-        for t in (self.cnt, self.sum):
-            x = t.to(_dev(group))
-            dist.all_reduce(x, op=dist.ReduceOp.SUM, group=group)
-            if x is not t:
-                t.copy_(x)
-        return self
-
     def numpy(self):
         """``{'count', 'rowsum', 'sum'}`` on the host, as ``reference_flux``
         returns them (waits for the pending calls)."""
         cnt = self.cnt.cpu().numpy()
         return {"count": np.ascontiguousarray(cnt[..., 0]), "rowsum": np.ascontiguousarray(cnt[..., 1]),
                 "sum": self.sum.cpu().numpy()}
-
-    @property
-    def lon_edges(self):
-        """The ``nx + 1`` longitude bin edges in degrees (those of
-        ``lon_range`` for an unwrapped map)."""
-        a, b = (0.0, 360.0) if self.spec.lon_range is None else (float(v) for v in self.spec.lon_range)
-        return np.linspace(a, b, self.spec.nx + 1)
-
-    lat_edges = D.DensityMap.lat_edges
 
     # ---- derived fields: device tensors [nchan, ny, nx], NaN where count == 0
     def _where_counted(self, x):
@@ -346,39 +256,23 @@ class FluxMap:
         float64 there (exact below 2^53), as int64 into an ``.npz``."""
         import ncio
         a = self.numpy()
-        s = self.spec
-        le, la = self.lon_edges, self.lat_edges
-        count, rowsum = a["count"], a["rowsum"]
-        if not str(ncfile).endswith(".npz"):
-            count, rowsum = count.astype(np.float64), rowsum.astype(np.float64)
-        dims = {"chan": s.nchan, "lat": s.ny, "lon": s.nx, "lat_edge": s.ny + 1, "lon_edge": s.nx + 1}
+        dims, v = self._grid_output()
         full = ("chan", "lat", "lon")
-        what = "unit vectors" if s.unit else "m s-1"
-        v = {"lon": (("lon",), 0.5 * (le[:-1] + le[1:]), "degrees"),
-             "lat": (("lat",), 0.5 * (la[:-1] + la[1:]), "degrees"),
-             "lon_edges": (("lon_edge",), le, "degrees"), "lat_edges": (("lat_edge",), la, "degrees"),
-             "count": (full, count, "ray points"), "rowsum": (full, rowsum, "sum of output rows"),
-             "fx": (full, np.ascontiguousarray(a["sum"][..., 0]), "sum of " + what),
-             "fy": (full, np.ascontiguousarray(a["sum"][..., 1]), "sum of " + what),
-             "fs": (full, np.ascontiguousarray(a["sum"][..., 2]), "sum of speeds, m s-1")}
+        what = "unit vectors" if self.spec.unit else "m s-1"
+        v.update({"count": (full, counts_for(ncfile, a["count"]), "ray points"),
+                  "rowsum": (full, counts_for(ncfile, a["rowsum"]), "sum of output rows"),
+                  "fx": (full, np.ascontiguousarray(a["sum"][..., 0]), "sum of " + what),
+                  "fy": (full, np.ascontiguousarray(a["sum"][..., 1]), "sum of " + what),
+                  "fs": (full, np.ascontiguousarray(a["sum"][..., 2]), "sum of speeds, m s-1")})
         ncio.write(ncfile, dims, v)
 
 
-class FluxSink(RowSink):
+class FluxSink(ChannelSink):
     """A ``sink`` of ``RayEngine.integrate`` / ``integrate_rk4`` / ``resume``
     and of ``shard.run_sharded`` (``launch_rows.RowSink``) that reduces each
     launch's rows into ``map``.  ``chan``: each ray's channel (length nray;
     with ``run_sharded`` indexed by the shard's ``idx``; None: channel 0); a
     ray with channel -1 contributes nothing."""
-
-    def __init__(self, map, chan=None):
-        super().__init__(map, None if chan is None else map._chan(chan, len(chan)))
-        self.map = map
-
-    chan = property(lambda self: self.per_ray)
-
-    def select(self, idx):
-        return None if self.per_ray is None else self.per_ray[idx]
 
 
 def select_through(summary, mode="any"):

@@ -20,7 +20,8 @@ import math
 import numpy as np
 
 import _hip as H
-from launch_rows import RowSink, one_row, row_args
+from launch_rows import one_row, row_args
+from raymap import ColumnSink, RayArgs
 
 R_EARTH = 6.3712e6      # metres: path_m = path * R_EARTH
 TWO_PI = 2 * math.pi
@@ -117,7 +118,7 @@ def reference_summary(rows, regions=None):
     return out
 
 
-class RaySummary:
+class RaySummary(RayArgs):
     """The device accumulators of ``nray`` rays: ``f64[9, nray]`` and
     ``i32[4 + 2 nreg, nray]`` (the layout of ``rwrt_ray_summary``,
     include/rwrt.h), set to the values of a ray without rows here and updated
@@ -154,17 +155,6 @@ class RaySummary:
             self.i32[k, cols] = v
         self.i32[H.SUMMARY_NI32:H.SUMMARY_NI32 + self.nreg, cols] = -1
         self.i32[H.SUMMARY_NI32 + self.nreg:, cols] = 0
-
-    def _ray(self, ray, n):
-        import torch
-        if ray is None:
-            if n != self.nray:
-                raise ValueError(f"{n} rays for {self.nray} columns: pass ray (each ray's column)")
-            return None
-        ray = torch.as_tensor(ray, device=self.device).to(torch.int64).contiguous()
-        if ray.numel() != n:
-            raise ValueError(f"ray has {ray.numel()} entries for {n} rays")
-        return ray
 
     def add_rows(self, i0, i1, view, tails=None, slots=None, ray=None):
         """Update the rays with rows ``[i0, i1)`` of a launch: ``view`` its row
@@ -301,21 +291,13 @@ class RaySummary:
         ncio.write(ncfile, dims, v)
 
 
-class SummarySink(RowSink):
+class SummarySink(ColumnSink):
     """A ``sink`` of ``RayEngine.integrate`` / ``integrate_rk4`` / ``resume``
     and of ``shard.run_sharded`` (``launch_rows.RowSink``) that updates
     ``summary`` from each launch's rows.  ``ray``: the column of each ray of
     the integration (None: ray j is column j); the sharded form's ``idx`` and
     ``take(idx)`` select from it, or are the columns themselves."""
-
-    def __init__(self, summary, ray=None):
-        super().__init__(summary, ray if ray is None else summary._ray(ray, len(ray)))
-        self.summary = summary
-
-    ray = property(lambda self: self.per_ray)
-
-    def select(self, idx):
-        return idx if self.per_ray is None else self.per_ray[idx]
+    summary = property(lambda self: self.target)
 
 
 class Tee:

@@ -26,16 +26,15 @@ from dataclasses import dataclass
 import numpy as np
 
 import _hip as H
-import density as D
-from flux import fold_arrays
-from launch_rows import RowSink, one_row, row_args
+from launch_rows import row_args
+from raymap import CarriedMap, ColumnSink, GridSpec, check_columns, counts_for, fold_arrays, valid_rows  # noqa: F401
 
 MODE_UNWRAPPED = 2
 TWO30 = float(2 ** 30)
 
 
 @dataclass(frozen=True)
-class TrackSpec:
+class TrackSpec(GridSpec):
     """``nx`` boxes over the longitude axis, ``ny`` over ``lat_range`` (degrees),
     ``nchan`` maps.  ``lon_range=None``: wrapped longitude, [0, 360);
     ``lon_range=(a, b)`` in degrees: the unwrapped window of a
@@ -55,62 +54,12 @@ class TrackSpec:
     max_cells: int = None
 
     def __post_init__(self):
-        if self.nx <= 0 or self.ny <= 0 or self.nchan <= 0:
-            raise ValueError("nx, ny and nchan must be positive")
-        if self.nx * self.ny * self.nchan >= 2 ** 31:
-            raise ValueError("nchan*ny*nx must be below 2^31")
-        if not self.lat_range[1] > self.lat_range[0]:
-            raise ValueError("lat_range must be ascending")
-        if self.lon_range is not None:
-            a, b = (float(v) for v in self.lon_range)
-            if not (math.isfinite(a) and math.isfinite(b) and b > a):
-                raise ValueError("lon_range must be None or finite and ascending")
-        for name in ("need", "weight"):
-            v = getattr(self, name)
-            if v is not None and v not in D.WEIGHT_COLUMNS:
-                raise ValueError(f"{name} must be None or one of {sorted(D.WEIGHT_COLUMNS)}")
+        self._check_shape()
+        self._check_ranges()
+        check_columns(self, "need", "weight")
         if self.max_cells is not None:
             if int(self.max_cells) != self.max_cells or not 1 <= self.max_cells < 2 ** 31:
                 raise ValueError("max_cells must be None or an integer in [1, 2^31)")
-
-    # pi * (deg / 180): +-90 give +-pi/2 exactly
-    @property
-    def lat0(self):
-        return math.pi * (float(self.lat_range[0]) / 180.0)
-
-    @property
-    def lat1(self):
-        return math.pi * (float(self.lat_range[1]) / 180.0)
-
-    @property
-    def unwrapped(self):
-        return self.lon_range is not None
-
-    @property
-    def lon0(self):
-        return math.pi * (float(self.lon_range[0]) / 180.0) if self.unwrapped else 0.0
-
-    @property
-    def lon1(self):
-        return math.pi * (float(self.lon_range[1]) / 180.0) if self.unwrapped else 2 * math.pi
-
-    # the factors of the grid coordinates: computed here, once, in fp64, and
-    # passed to the kernel (never recomputed on the device)
-    @property
-    def inv_dlon(self):
-        return self.nx / (self.lon1 - self.lon0)
-
-    @property
-    def inv_dlat(self):
-        return self.ny / (self.lat1 - self.lat0)
-
-    @property
-    def ncol(self):
-        return -1 if self.need is None else D.WEIGHT_COLUMNS[self.need]
-
-    @property
-    def wcol(self):
-        return -1 if self.weight is None else D.WEIGHT_COLUMNS[self.weight]
 
     @property
     def cells(self):
@@ -119,20 +68,6 @@ class TrackSpec:
     @property
     def mode(self):
         return MODE_UNWRAPPED if self.unwrapped else 0
-
-    @property
-    def shape(self):
-        return (self.nchan, self.ny, self.nx)
-
-    @property
-    def circles(self):
-        """The whole circles of an unwrapped window that starts on a multiple
-        of 360 degrees; None for any other axis (``flux.FluxSpec.circles``)."""
-        if not self.unwrapped:
-            return None
-        a, b = (float(v) for v in self.lon_range)
-        n = (b - a) / 360.0
-        return int(n) if a % 360.0 == 0.0 and n == int(n) else None
 
     def c_struct(self):
         return H.TrackMapC(self.nx, self.ny, self.nchan, self.mode, self.ncol, self.wcol, self.cells, 0,
@@ -184,16 +119,6 @@ def segment_cells(X0, Y0, X1, Y1, max_cells):
             ncy -= 1
     out.append((ix, iy, 1.0 - t))
     return out
-
-
-def valid_rows(rows, spec):
-    """``[nray, nt]`` bool: lon and lat finite and, with ``need`` / ``weight``,
-    those columns finite too."""
-    ok = np.isfinite(rows[..., 0]) & np.isfinite(rows[..., 1])
-    for col in (spec.ncol, spec.wcol):
-        if col >= 0:
-            ok &= np.isfinite(rows[..., col])
-    return ok
 
 
 def deposits(rows, chan, spec):
@@ -272,53 +197,24 @@ def reference_track(rows, chan, spec):
     return {"cnt": cnt, "time": time, "wsum": wsum, "dropped": dropped}
 
 
-class TrackMap:
+class TrackMap(CarriedMap):
     """The device arrays of one map over ``nray`` rays: ``cnt`` (int64),
     ``time`` and ``wsum`` (fp64; ``wsum`` None without a weight), each
     ``[nchan, ny, nx]``, and ``dropped`` (int64 ``[1]``), zeroed here and
-    accumulated into by every ``add_rows`` call (time chunks, shards); and
-    ``prev`` (fp64 ``[3, nray]``: lon, lat, weight value), each ray's carried
-    previous row, NaN for none.  ``prev`` is a running state, not a sum: a
-    ray's rows must arrive once, in order, each call starting at the row the
-    previous one ended with (``start`` is row 0).  ``chan``: each ray's
-    channel, indexed by the ray's column (None: channel 0); a ray with a
-    channel outside ``[0, nchan)`` contributes nothing."""
+    accumulated into by every ``add_rows`` call (time chunks, shards);
+    ``allreduce`` sums them over the ranks.  The carried rows (``prev``,
+    ``start``, ``restart``) and ``chan`` are ``raymap.CarriedMap``'s and are
+    not reduced; a ray with a channel outside ``[0, nchan)`` contributes
+    nothing."""
+    REDUCE = (("cnt", "SUM"), ("time", "SUM"), ("wsum", "SUM"), ("dropped", "SUM"))
 
     def __init__(self, spec, nray, device=None, chan=None):
         import torch
-        H.require_gpu()
-        H.load()
-        self.spec = spec
-        self.nray = int(nray)
-        self.device = torch.device(device or "cuda")
+        super().__init__(spec, nray, device, chan)
         self.cnt = torch.zeros(spec.shape, dtype=torch.int64, device=self.device)
         self.time = torch.zeros(spec.shape, dtype=torch.float64, device=self.device)
         self.wsum = torch.zeros(spec.shape, dtype=torch.float64, device=self.device) if spec.wcol >= 0 else None
         self.dropped = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.prev = torch.full((3, self.nray), math.nan, dtype=torch.float64, device=self.device)
-        self.chan = None
-        if chan is not None:
-            self.chan = torch.as_tensor(chan, device=self.device).to(torch.int32).contiguous()
-            if self.chan.numel() != self.nray:
-                raise ValueError(f"chan has {self.chan.numel()} entries for {self.nray} rays")
-        self._c = spec.c_struct()
-        self._lib = H.load()      # (tools/track_rate.py puts an A/B build here)
-
-    def restart(self):
-        """Forget every ray's carried row (the maps stay)."""
-        self.prev.fill_(math.nan)
-        return self
-
-    def _ray(self, ray, n):
-        import torch
-        if ray is None:
-            if n != self.nray:
-                raise ValueError(f"{n} rays for {self.nray} columns: pass ray (each ray's column)")
-            return None
-        ray = torch.as_tensor(ray, device=self.device).to(torch.int64).contiguous()
-        if ray.numel() != n:
-            raise ValueError(f"ray has {ray.numel()} entries for {n} rays")
-        return ray
 
     def add_rows(self, i0, i1, view, tails=None, slots=None, ray=None):
         """Deposit the segments that end on rows ``[i0, i1)`` of a launch:
@@ -335,49 +231,12 @@ class TrackMap:
             H.dptr(self.prev, torch.float64), H.dptr(self.cnt, torch.int64), H.dptr(self.time, torch.float64),
             H.dptr(self.wsum), H.dptr(self.dropped, torch.int64), H.stream(self.device)))
 
-    def start(self, lon, lat, need=None, v=None, ray=None):
-        """Row 0, the initial rays (radians), which sinks never receive: the
-        same entry point on a ``[n, 1, 8]`` row tensor; it deposits nothing
-        and sets the carried rows.  ``need`` / ``v``: the values of the
-        ``need`` and ``weight`` columns (required when the spec names them)."""
-        cols = {0: lon, 1: lat}
-        for name, col, val in (("need", self.spec.ncol, need), ("weight", self.spec.wcol, v)):
-            if col >= 0:
-                if val is None:
-                    raise ValueError(f"the map's {name} column is {getattr(self.spec, name)!r}: pass its values")
-                cols[col] = val
-        self.add_rows(0, 1, one_row(cols, self.device), ray=ray)
-        return self
-
-    def allreduce(self, group=None):
-        """SUM of the maps and of ``dropped`` over the ranks of ``group``, left
-        on every rank.  The carried rows are not reduced."""
-        import torch.distributed as dist
-        from shard import _dev
-        for t in (self.cnt, self.time, self.wsum, self.dropped):
-            if t is None:
-                continue
-            x = t.to(_dev(group))
-            dist.all_reduce(x, op=dist.ReduceOp.SUM, group=group)
-            if x is not t:
-                t.copy_(x)
-        return self
-
     def numpy(self):
         """``{'cnt', 'time', 'wsum', 'dropped'}`` on the host, as
         ``reference_track`` returns them (waits for the pending calls)."""
         return {"cnt": self.cnt.cpu().numpy(), "time": self.time.cpu().numpy(),
                 "wsum": None if self.wsum is None else self.wsum.cpu().numpy(),
                 "dropped": int(self.dropped.cpu().numpy()[0])}
-
-    @property
-    def lon_edges(self):
-        """The ``nx + 1`` longitude box edges in degrees (those of
-        ``lon_range`` for an unwrapped map)."""
-        a, b = (0.0, 360.0) if self.spec.lon_range is None else (float(v) for v in self.spec.lon_range)
-        return np.linspace(a, b, self.spec.nx + 1)
-
-    lat_edges = D.DensityMap.lat_edges
 
     # ---- derived fields: device tensors [nchan, ny, nx]
     def seconds(self, tstep):
@@ -411,34 +270,21 @@ class TrackMap:
         (exact below 2^53), as int64 into an ``.npz``."""
         import ncio
         a = self.numpy()
-        s = self.spec
-        le, la = self.lon_edges, self.lat_edges
-        cnt = a["cnt"] if str(ncfile).endswith(".npz") else a["cnt"].astype(np.float64)
-        dims = {"chan": s.nchan, "lat": s.ny, "lon": s.nx, "lat_edge": s.ny + 1, "lon_edge": s.nx + 1, "one": 1}
+        dims, v = self._grid_output()
+        dims["one"] = 1
         full = ("chan", "lat", "lon")
-        v = {"lon": (("lon",), 0.5 * (le[:-1] + le[1:]), "degrees"),
-             "lat": (("lat",), 0.5 * (la[:-1] + la[1:]), "degrees"),
-             "lon_edges": (("lon_edge",), le, "degrees"), "lat_edges": (("lat_edge",), la, "degrees"),
-             "cnt": (full, cnt, "box visits"), "time": (full, a["time"], "row intervals"),
-             "dropped": (("one",), np.array([float(a["dropped"])]), "segments")}
+        v.update({"cnt": (full, counts_for(ncfile, a["cnt"]), "box visits"),
+                  "time": (full, a["time"], "row intervals"),
+                  "dropped": (("one",), np.array([float(a["dropped"])]), "segments")})
         if a["wsum"] is not None:
-            v["wsum"] = (full, a["wsum"], f"time integral of {s.weight}, row intervals")
+            v["wsum"] = (full, a["wsum"], f"time integral of {self.spec.weight}, row intervals")
         ncio.write(ncfile, dims, v)
 
 
-class TrackSink(RowSink):
+class TrackSink(ColumnSink):
     """A ``sink`` of ``RayEngine.integrate`` / ``integrate_rk4`` / ``resume``
     and of ``shard.run_sharded`` (``launch_rows.RowSink``) that deposits each
     launch's segments into ``map``.  ``ray``: the column of each ray of the
     integration (None: ray j is column j); the sharded form's ``idx`` and
     ``take(idx)`` select from it, or are the columns themselves.  Channels are
     the map's (``TrackMap.chan``), indexed by column."""
-
-    def __init__(self, map, ray=None):
-        super().__init__(map, ray if ray is None else map._ray(ray, len(ray)))
-        self.map = map
-
-    ray = property(lambda self: self.per_ray)
-
-    def select(self, idx):
-        return idx if self.per_ray is None else self.per_ray[idx]

@@ -240,6 +240,48 @@ class WR:
         self.last_run = res
         return res
 
+    # ---- the products reduced on the device (raymap.py): what the ray_* methods share
+    def _channels(self, spec, by):
+        """``(spec, chan)`` for ``by``: the spec with one map per zonal
+        wavenumber or root and the channel of every ray slot (None: one map)."""
+        import raymap
+        _check_by(by)
+        if by is None:
+            return spec, None
+        ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
+        chan = np.ascontiguousarray(np.broadcast_to(ax, (3, self.nsource, self.nzwn))).reshape(-1).astype(np.int32)
+        return raymap.with_channels(spec, self.nzwn if by == "zwn" else 3), chan
+
+    def _column(self, col, rows=0):
+        """Rows ``rows`` of the history array of row column ``col`` (2..6); None for -1."""
+        return None if col < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[col - 2][rows]
+
+    def _history_rows(self, inte_method, root_method, group):
+        """``ray_run`` on the GPU and its history as rows ``[nray, nt, 8]``
+        (the ``mode='numpy'`` products apply their reference to it)."""
+        self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
+        nray = 3 * self.nsource * self.nzwn
+        rows = np.full((nray, self.nt, 8), np.nan)
+        for c, h in enumerate((self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)):
+            rows[:, :, c] = h.reshape(self.nt, nray).T
+        return rows
+
+    def _reduce_on_device(self, make, mode, inte_method, group, root_method):
+        """Initialise the rays, integrate them into the sink of ``make(rank,
+        device) -> (product, sink)`` -- which also hands row 0 to the product
+        -- and combine the ranks' products."""
+        import shard
+        key = mode + "_rk45" if inte_method == "rk45" else mode
+        if key not in SUPPORTED:
+            self.core_ray_run(key)     # raises before any work
+        self.ray_initial(mode=mode, root_method=root_method)
+        rank, world = shard.world_info(group) if group is not None else (0, 1)
+        product, sink = make(rank, self.bs.engine().device)
+        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=sink)
+        if group is not None and shard.collective(world):
+            product.allreduce(group)
+        return product
+
     def ray_density(self, spec, mode="hip", inte_method="rk45", by=None, include_initial=True,
                     group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but bin every
@@ -256,35 +298,19 @@ class WR:
         ``(count, wsum)``).  With a process ``group`` every rank ends with the
         sum over the ranks."""
         import density as D
-        if by not in (None, "zwn", "root"):
-            raise ValueError("by must be None, 'zwn' or 'root'")
-        shape = (3, self.nsource, self.nzwn)
-        chan = None
-        if by is not None:
-            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
-            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
-            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
+        spec, chan = self._channels(spec, by)
         if mode == "numpy":
-            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
-            w = None if spec.wcol < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[spec.wcol - 2]
-            first = 0 if include_initial else 1
-            nray = 3 * self.nsource * self.nzwn
-            pts = [None if a is None else a[first:].reshape(-1, nray) for a in (self.rlon, self.rlat, w)]
-            return D.reference_bins(pts[0], pts[1], pts[2], None if chan is None else chan[None, :], spec)
-        key = mode + "_rk45" if inte_method == "rk45" else mode
-        if key not in SUPPORTED:
-            self.core_ray_run(key)     # raises before any work
-        self.ray_initial(mode=mode, root_method=root_method)
-        import shard
-        rank, world = shard.world_info(group) if group is not None else (0, 1)
-        dmap = D.DensityMap(spec, self.bs.engine().device)
-        if include_initial and rank == 0:
-            w0 = None if spec.wcol < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[spec.wcol - 2][0]
-            dmap.add_points(self.rlon[0], self.rlat[0], w0, chan)
-        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=D.DensitySink(dmap, chan))
-        if group is not None and shard.collective(world):
-            dmap.allreduce(group)
-        return dmap
+            rows = self._history_rows(inte_method, root_method, group)[:, 0 if include_initial else 1:]
+            return D.reference_bins(rows[..., 0].T, rows[..., 1].T, None if spec.wcol < 0 else rows[..., spec.wcol].T,
+                                    None if chan is None else chan[None, :], spec)
+
+        def make(rank, device):
+            dmap = D.DensityMap(spec, device)
+            if include_initial and rank == 0:
+                dmap.add_points(self.rlon[0], self.rlat[0], self._column(spec.wcol), chan)
+            return dmap, D.DensitySink(dmap, chan)
+
+        return self._reduce_on_device(make, mode, inte_method, group, root_method)
 
     def ray_arrival(self, spec, mode="hip", inte_method="rk45", by=None, include_initial=True,
                     group=None, root_method="numpy"):
@@ -300,42 +326,24 @@ class WR:
         ``arrival.reference_arrival`` on the host (small runs; returns its
         dict).  With a process ``group`` every rank ends with the reduced map."""
         import arrival as A
-        import density as D
-        if by not in (None, "zwn", "root"):
-            raise ValueError("by must be None, 'zwn' or 'root'")
+        _check_by(by)
         if spec.nt != self.nt:
             raise ValueError(f"spec.nt is {spec.nt}, the run has {self.nt} rows")
-        shape = (3, self.nsource, self.nzwn)
-        nray = 3 * self.nsource * self.nzwn
-        chan = None
-        if by is not None:
-            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
-            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
-            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
+        spec, chan = self._channels(spec, by)
         col = spec.bins.wcol
-
-        def required(rows):
-            return None if col < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[col - 2][rows]
-
         if mode == "numpy":
-            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
             first = 0 if include_initial else 1
-            pts = [None if a is None else a.reshape(-1, nray).T
-                   for a in (self.rlon[first:], self.rlat[first:], required(slice(first, None)))]
-            return A.reference_arrival(pts[0], pts[1], pts[2], chan, spec, row0=first)
-        key = mode + "_rk45" if inte_method == "rk45" else mode
-        if key not in SUPPORTED:
-            self.core_ray_run(key)     # raises before any work
-        self.ray_initial(mode=mode, root_method=root_method)
-        import shard
-        rank, world = shard.world_info(group) if group is not None else (0, 1)
-        amap = A.ArrivalMap(spec, self.bs.engine().device)
-        if include_initial and rank == 0:
-            amap.add_points(self.rlon[0], self.rlat[0], required(0), chan)
-        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=A.ArrivalSink(amap, chan))
-        if group is not None and shard.collective(world):
-            amap.allreduce(group)
-        return amap
+            rows = self._history_rows(inte_method, root_method, group)[:, first:]
+            return A.reference_arrival(rows[..., 0], rows[..., 1], None if col < 0 else rows[..., col], chan, spec,
+                                       row0=first)
+
+        def make(rank, device):
+            amap = A.ArrivalMap(spec, device)
+            if include_initial and rank == 0:
+                amap.add_points(self.rlon[0], self.rlat[0], self._column(col), chan)
+            return amap, A.ArrivalSink(amap, chan)
+
+        return self._reduce_on_device(make, mode, inte_method, group, root_method)
 
     def ray_flux(self, spec, mode="hip", inte_method="rk45", by=None, through=None, through_mode="any",
                  include_initial=True, group=None, root_method="numpy"):
@@ -360,62 +368,60 @@ class WR:
         selection) on the host (small runs; returns the dict of
         ``reference_flux`` with ``'selected'`` added).  With a process
         ``group`` every rank ends with the sum over the ranks."""
-        import density as D
         import flux as F
-        if by not in (None, "zwn", "root"):
-            raise ValueError("by must be None, 'zwn' or 'root'")
+        _check_by(by)
         if through_mode not in ("any", "all"):
             raise ValueError("through_mode must be 'any' or 'all'")
         if through is not None and not 1 <= len(through) <= 8:
             raise ValueError("through must be None or 1 to 8 boxes (lon_w, lon_e, lat_s, lat_n)")
+        spec, chan = self._channels(spec, by)
         shape = (3, self.nsource, self.nzwn)
-        nray = 3 * self.nsource * self.nzwn
-        chan = None
-        if by is not None:
-            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
-            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
-            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
 
         def only(selected):      # channel -1 for the rays that do not pass
             return np.where(selected, 0 if chan is None else chan, -1).astype(np.int32)
 
+        selected = None
         if mode == "numpy":
-            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
-            hist = (self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)
-            selected = None
+            rows = self._history_rows(inte_method, root_method, group)
             if through is not None:
                 import summary as Sm
-                rows = np.full((nray, self.nt, 8), np.nan)
-                for c, h in enumerate(hist):
-                    rows[:, :, c] = h.reshape(self.nt, nray).T
                 first_row = Sm.reference_summary(rows, through)["first_row"] >= 0
                 selected = first_row.any(axis=0) if through_mode == "any" else first_row.all(axis=0)
                 chan = only(selected)
             first = 0 if include_initial else 1
-            pts = [hist[c][first:].reshape(-1, nray).T for c in (0, 1, 2, 3, 5, 6)]
-            out = F.reference_flux(*pts, chan, spec, row0=first)
+            out = F.reference_flux(*(rows[:, first:, c] for c in (0, 1, 2, 3, 5, 6)), chan, spec, row0=first)
             out["selected"] = None if selected is None else selected.reshape(shape)
             return out
-        key = mode + "_rk45" if inte_method == "rk45" else mode
-        if key not in SUPPORTED:
-            self.core_ray_run(key)     # raises before any work
-        selected = None
         if through is not None:
+            # (validates mode / inte_method before any work, like _reduce_on_device)
             rs = self.ray_summary(regions=through, mode=mode, inte_method=inte_method, group=group,
                                   root_method=root_method)
             selected = F.select_through(rs, through_mode).cpu().numpy()
             chan = only(selected)
-        self.ray_initial(mode=mode, root_method=root_method)
-        import shard
-        rank, world = shard.world_info(group) if group is not None else (0, 1)
-        fmap = F.FluxMap(spec, self.bs.engine().device)
-        fmap.selected = None if selected is None else selected.reshape(shape)
-        if include_initial and rank == 0:
-            fmap.add_points(self.rlon[0], self.rlat[0], self.rzwn[0], self.rmwn[0], self.rug[0], self.rvg[0], chan)
-        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=F.FluxSink(fmap, chan))
-        if group is not None and shard.collective(world):
-            fmap.allreduce(group)
-        return fmap
+
+        def make(rank, device):
+            fmap = F.FluxMap(spec, device)
+            fmap.selected = None if selected is None else selected.reshape(shape)
+            if include_initial and rank == 0:
+                fmap.add_points(self.rlon[0], self.rlat[0], self.rzwn[0], self.rmwn[0], self.rug[0], self.rvg[0], chan)
+            return fmap, F.FluxSink(fmap, chan)
+
+        return self._reduce_on_device(make, mode, inte_method, group, root_method)
+
+    def _ray_segments(self, reference, Map, Sink, spec, mode, inte_method, by, group, root_method):
+        """``ray_track`` / ``ray_cross``: the product's reference function,
+        its ``raymap.CarriedMap`` and its sink."""
+        spec, chan = self._channels(spec, by)
+        if mode == "numpy":
+            return reference(self._history_rows(inte_method, root_method, group), chan, spec)
+
+        def make(rank, device):
+            m = Map(spec, 3 * self.nsource * self.nzwn, device, chan)
+            # row 0 on every rank: the rank that integrates a ray carries it into row 1
+            m.start(self.rlon[0], self.rlat[0], self._column(spec.ncol), self._column(spec.wcol))
+            return m, Sink(m)
+
+        return self._reduce_on_device(make, mode, inte_method, group, root_method)
 
     def ray_track(self, spec, mode="hip", inte_method="rk45", by=None, group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but deposit the
@@ -430,40 +436,8 @@ class WR:
         history and applies ``track.reference_track`` on the host (small runs;
         returns its dict).  With a process ``group`` every rank ends with the
         sum over the ranks."""
-        import density as D
         import track as T
-        if by not in (None, "zwn", "root"):
-            raise ValueError("by must be None, 'zwn' or 'root'")
-        shape = (3, self.nsource, self.nzwn)
-        nray = 3 * self.nsource * self.nzwn
-        chan = None
-        if by is not None:
-            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
-            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
-            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
-        if mode == "numpy":
-            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
-            rows = np.full((nray, self.nt, 8), np.nan)
-            for c, h in enumerate((self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)):
-                rows[:, :, c] = h.reshape(self.nt, nray).T
-            return T.reference_track(rows, chan, spec)
-        key = mode + "_rk45" if inte_method == "rk45" else mode
-        if key not in SUPPORTED:
-            self.core_ray_run(key)     # raises before any work
-        self.ray_initial(mode=mode, root_method=root_method)
-        import shard
-        world = shard.world_info(group)[1] if group is not None else 1
-        tmap = T.TrackMap(spec, nray, self.bs.engine().device, chan)
-
-        def column(col):
-            return None if col < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[col - 2][0]
-
-        # row 0 on every rank: the rank that integrates a ray carries it into row 1
-        tmap.start(self.rlon[0], self.rlat[0], column(spec.ncol), column(spec.wcol))
-        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=T.TrackSink(tmap))
-        if group is not None and shard.collective(world):
-            tmap.allreduce(group)
-        return tmap
+        return self._ray_segments(T.reference_track, T.TrackMap, T.TrackSink, spec, mode, inte_method, by, group, root_method)
 
     def ray_cross(self, spec, mode="hip", inte_method="rk45", by=None, group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but test the
@@ -482,39 +456,7 @@ class WR:
         returns its dict).  With a process ``group`` every rank ends with the
         sum over the ranks."""
         import cross as X
-        import density as D
-        if by not in (None, "zwn", "root"):
-            raise ValueError("by must be None, 'zwn' or 'root'")
-        shape = (3, self.nsource, self.nzwn)
-        nray = 3 * self.nsource * self.nzwn
-        chan = None
-        if by is not None:
-            spec = D.with_channels(spec, self.nzwn if by == "zwn" else 3)
-            ax = np.arange(self.nzwn)[None, None, :] if by == "zwn" else np.arange(3)[:, None, None]
-            chan = np.ascontiguousarray(np.broadcast_to(ax, shape)).reshape(-1).astype(np.int32)
-        if mode == "numpy":
-            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
-            rows = np.full((nray, self.nt, 8), np.nan)
-            for c, h in enumerate((self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)):
-                rows[:, :, c] = h.reshape(self.nt, nray).T
-            return X.reference_cross(rows, chan, spec)
-        key = mode + "_rk45" if inte_method == "rk45" else mode
-        if key not in SUPPORTED:
-            self.core_ray_run(key)     # raises before any work
-        self.ray_initial(mode=mode, root_method=root_method)
-        import shard
-        world = shard.world_info(group)[1] if group is not None else 1
-        xmap = X.CrossMap(spec, nray, self.bs.engine().device, chan)
-
-        def column(col):
-            return None if col < 0 else (self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)[col - 2][0]
-
-        # row 0 on every rank: the rank that integrates a ray carries it into row 1
-        xmap.start(self.rlon[0], self.rlat[0], column(spec.ncol), column(spec.wcol))
-        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=X.CrossSink(xmap))
-        if group is not None and shard.collective(world):
-            xmap.allreduce(group)
-        return xmap
+        return self._ray_segments(X.reference_cross, X.CrossMap, X.CrossSink, spec, mode, inte_method, by, group, root_method)
 
     def ray_summary(self, regions=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but reduce every
@@ -533,30 +475,21 @@ class WR:
         summary."""
         import summary as Sm
         shape = (3, self.nsource, self.nzwn)
-        nray = 3 * self.nsource * self.nzwn
         if mode == "numpy":
-            self.ray_run(mode="hip", inte_method=inte_method, root_method=root_method, group=group)
-            rows = np.full((nray, self.nt, 8), np.nan)
-            for c, h in enumerate((self.rlon, self.rlat, self.rzwn, self.rmwn, self.ramp, self.rug, self.rvg)):
-                rows[:, :, c] = h.reshape(self.nt, nray).T
+            rows = self._history_rows(inte_method, root_method, group)
             rs = Sm.RaySummary.from_fields(Sm.reference_summary(rows, regions), self.nt, regions or (),
                                            self.bs.engine().device)
             rs.shape = shape
             return rs
-        key = mode + "_rk45" if inte_method == "rk45" else mode
-        if key not in SUPPORTED:
-            self.core_ray_run(key)     # raises before any work
-        self.ray_initial(mode=mode, root_method=root_method)
-        import shard
-        world = shard.world_info(group)[1] if group is not None else 1
-        rs = Sm.RaySummary(nray, regions or (), self.bs.engine().device)
-        rs.shape = shape
-        # row 0 on every rank: the rank that integrates a ray carries it into row 1
-        rs.start(self.rlon[0], self.rlat[0], self.rmwn[0], self.ramp[0])
-        self._core_ray_run_hip("rk45" if key == "hip_rk45" else "rk4", group, sink=Sm.SummarySink(rs))
-        if group is not None and shard.collective(world):
-            rs.allreduce(group)
-        return rs
+
+        def make(rank, device):
+            rs = Sm.RaySummary(3 * self.nsource * self.nzwn, regions or (), device)
+            rs.shape = shape
+            # row 0 on every rank: the rank that integrates a ray carries it into row 1
+            rs.start(self.rlon[0], self.rlat[0], self.rmwn[0], self.ramp[0])
+            return rs, Sm.SummarySink(rs)
+
+        return self._reduce_on_device(make, mode, inte_method, group, root_method)
 
     def core_ray_run(self, mode="hip_rk45", group=None):
         if mode not in SUPPORTED:
@@ -653,6 +586,11 @@ def initial_rows(bs, source_lon, source_lat, zwn, freq, root_method="numpy"):
         amp[:, :, iz] = a
         ug[:, :, iz], vg[:, :, iz] = cal_ugvg(fmu, fmv, fmqx, fmqy, kz, m_val, mode="numpy")
     return lon, lat, k, m, amp, ug, vg
+
+
+def _check_by(by):
+    if by not in (None, "zwn", "root"):
+        raise ValueError("by must be None, 'zwn' or 'root'")
 
 
 def _default_chunk(nray, nt):

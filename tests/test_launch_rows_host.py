@@ -11,9 +11,18 @@ import pytest
 import torch
 
 import launch_rows
+from arrival import ArrivalSink
+from cross import CrossSink
 from density import DensitySink
 from engine import deliver
+from flux import FluxSink
 from summary import SummarySink
+from track import TrackSink
+
+# the six sinks: a channel per ray (None stays None), or a column per ray (None: idx itself)
+CHANNEL_SINKS = {"density": DensitySink, "arrival": ArrivalSink, "flux": FluxSink}
+COLUMN_SINKS = {"summary": SummarySink, "track": TrackSink, "cross": CrossSink}
+SINKS = {**CHANNEL_SINKS, **COLUMN_SINKS}
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NRAY, I0, I1, NOUT = 16, 3, 10, 8          # 7 rows: one batch of 4 and a remainder of 3
@@ -131,17 +140,17 @@ def _same_call(got, i0, i1, view, tails, slots, per_ray):
         assert got[5].dtype == per_ray.dtype and torch.equal(got[5], per_ray)
 
 
-@pytest.mark.parametrize("kind", ["density", "summary"])
+@pytest.mark.parametrize("kind", list(SINKS))
 @pytest.mark.parametrize("with_attr", [False, True])
 def test_every_call_form_reaches_add_rows(kind, with_attr):
     t = FakeTarget()
     attr = [5, 6, 7, 8, 9, 10] if with_attr else None
-    sink = DensitySink(t, attr) if kind == "density" else SummarySink(t, attr)
-    dt = torch.int32 if kind == "density" else torch.int64
+    sink = SINKS[kind](t, attr)
+    dt = torch.int32 if kind in CHANNEL_SINKS else torch.int64
     whole = None if attr is None else torch.tensor(attr, dtype=dt)
     assert sink.takes_tails and sink.takes_slots
-    assert (sink.chan if kind == "density" else sink.ray) is sink.per_ray
-    assert (sink.map if kind == "density" else sink.summary) is t
+    assert (sink.chan if kind in CHANNEL_SINKS else sink.ray) is sink.per_ray
+    assert (sink.summary if kind == "summary" else sink.map) is t
     view, tails, slots = "view", "tails", "slots"        # (passed through untouched)
     forms = [((), {}, None, None), ((tails,), {}, tails, None), ((tails, slots), {}, tails, slots),
              ((), dict(tails=tails), tails, None), ((), dict(tails=tails, slots=slots), tails, slots),
@@ -152,7 +161,7 @@ def test_every_call_form_reaches_add_rows(kind, with_attr):
     # the sharded form: idx as a tensor and as a NumPy array
     for idx in (torch.tensor([4, 0, 2]), np.array([1, 5])):
         cols = torch.as_tensor(idx).to(torch.int64)
-        if kind == "density":
+        if kind in CHANNEL_SINKS:
             sub = None if whole is None else whole[cols]
         else:
             sub = cols if whole is None else whole[cols]
@@ -161,10 +170,10 @@ def test_every_call_form_reaches_add_rows(kind, with_attr):
             _same_call(t.calls[-1], 1, 5, view, want_t, want_s, sub)
 
 
-@pytest.mark.parametrize("kind", ["density", "summary"])
+@pytest.mark.parametrize("kind", list(SINKS))
 def test_shard_cache_is_keyed_by_the_idx_object(kind):
     t = FakeTarget()
-    sink = (DensitySink if kind == "density" else SummarySink)(t, [5, 6, 7, 8])
+    sink = SINKS[kind](t, [5, 6, 7, 8])
     idx = torch.tensor([2, 0])
     sink(1, 5, "v", idx)
     sink(6, 9, "v", idx, "tails")
@@ -191,6 +200,12 @@ def test_take_composes():
     part = whole.take([1])
     part(1, 5, "v", torch.tensor([0]))
     assert whole._sub == (None, None) and whole.ray.tolist() == [5, 6, 7]  # take leaves the sink it came from
+    for kind, cls in SINKS.items():                                       # each of the six keeps its class
+        took = cls(t, [5, 6, 7, 8, 9]).take([4, 1, 0]).take(torch.tensor([2, 0]))
+        assert type(took) is cls and took.target is t and took.per_ray.tolist() == [5, 9] and took._sub == (None, None)
+        assert not any(issubclass(cls, other) for other in SINKS.values() if other is not cls)   # distinct classes
+        none = cls(t).take([1, 0]).per_ray
+        assert none is None if kind in CHANNEL_SINKS else none.tolist() == [1, 0]
 
 
 class FakeEngine:
