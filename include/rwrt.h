@@ -311,8 +311,11 @@ rwrt_status rwrt_rk45_run(rwrt_ctx* ctx, const rwrt_grid* g, const double* d_pac
  *    it is in d_out).  This build gives the rays frozen at the call's start
  *    it_begin and every other ray it_end (a ray that freezes during the call
  *    writes its remaining rows, as rwrt_rk45_run does).
- *  d_tail_row[nray][8] (16-byte aligned): the tail row of ray j (meaningful
- *    where d_tail_from[j] < it_end).
+ *  d_tail_row[nray][8] (16-byte aligned): ray j's last row of the call, row
+ *    it_end - 1 -- its tail row where d_tail_from[j] < it_end, and for every
+ *    other ray the row the call wrote last into d_out (stored where the ray's
+ *    state is written back), so a caller that wants the end points of a call
+ *    reads them here whatever the layout of d_out.
  * rwrt_expand_tails writes the tails into d_out for a consumer that wants the
  * rows dense: then d_out equals rwrt_rk45_run's bit for bit, as do the state,
  * counters and nanrow after every call.  NULL d_tail_from and d_tail_row:
@@ -358,6 +361,32 @@ rwrt_status rwrt_rk45_run_slots(rwrt_ctx* ctx, const rwrt_grid* g, const double*
 rwrt_status rwrt_expand_slots(int64_t nray, int32_t it_begin, int32_t it_end, const int32_t* d_row_slot,
                               const int32_t* d_tail_from, const double* d_tail_row, const double* d_rows,
                               double* d_out, void* stream);
+
+/* ABI 5, additive: what orders a ray-loop call, decided in one call.  From the
+ * state and counters a previous call left, for every ray j:
+ *  d_work[j] (int64) := d_count[j][0] + d_count[j][1] - d_prev_work[j], the
+ *    attempts since the call d_prev_work was taken before (RWRT_PLAN_SINCE),
+ *    or every attempt so far (RWRT_PLAN_TOTAL); then
+ *  d_prev_work[j] := d_count[j][0] + d_count[j][1] (in and out; it must not
+ *    exceed the counters on entry: work is not negative);
+ *  d_row_slot[nray], d_nslot[0]: exactly what rwrt_row_slots gives on d_state;
+ *  d_order[nray] (int64): the rays live now (rwrt_row_slots' test) by
+ *    descending d_work, equal work in ascending ray index, then the frozen
+ *    rays in ascending ray index -- the d_order of a rwrt_rk45_run* call that
+ *    starts its longest rays first;
+ *  h_nlive[0] (int64, HOST memory) := the number of live rays (= d_nslot[0]).
+ * The call runs a fixed number of small kernels and a radix sort of the live
+ * rays over the bits of the largest d_work on `stream`, and waits on the
+ * stream once (for h_nlive).  d_scratch: rwrt_launch_plan_bytes(nray) bytes
+ * of device memory, 256-byte aligned, the caller's (contents do not matter;
+ * a larger buffer serves a smaller nray). */
+#define RWRT_PLAN_SINCE 0
+#define RWRT_PLAN_TOTAL 1
+rwrt_status rwrt_launch_plan_bytes(int64_t nray, int64_t* bytes);
+rwrt_status rwrt_launch_plan(int64_t nray, int32_t policy, const double* d_state,
+                             const int64_t* d_count, int64_t* d_prev_work, int64_t* d_work,
+                             int64_t* d_order, int32_t* d_row_slot, int64_t* d_nslot,
+                             int64_t* h_nlive, void* d_scratch, int64_t scratch_bytes, void* stream);
 
 /* ABI 5: ray-density maps.  The output rows of a ray-loop call are binned
  * where they lie instead of being shipped to the host: how many ray points

@@ -20,6 +20,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_mercator_point", "rwrt_rhs", "rwrt_dp54_attempt",
                "rwrt_ray_initial", "rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails",
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
+               "rwrt_launch_plan_bytes", "rwrt_launch_plan",
                "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival", "rwrt_ray_flux",
                "rwrt_ray_track", "rwrt_ray_cross",
                "rwrt_wn_map", "rwrt_wn_fill",
@@ -29,6 +30,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_kat_rk45", "rwrt_selftest_math", "rwrt_host_fill_rows")
 
 RWRT_OK, RWRT_ERR_ARG, RWRT_ERR_HIP, RWRT_SOLVER_FAILED = 0, 1, 2, 3
+PLAN_SINCE, PLAN_TOTAL = 0, 1   # RWRT_PLAN_SINCE, RWRT_PLAN_TOTAL
 
 
 class RwrtError(RuntimeError):
@@ -166,6 +168,8 @@ def load():
         "rwrt_rk45_run_slots": [_P, G, _P, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P],
         "rwrt_expand_slots": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P],
+        "rwrt_launch_plan_bytes": [_I64, ctypes.POINTER(_I64)],
+        "rwrt_launch_plan": [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(_I64), _P, _I64, _P],
         "rwrt_rk4_run": [_P, G, _P, _I64, Pr, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_density": [M, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_arrival": [A, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -281,6 +285,28 @@ class Context:
         else:
             check(load().rwrt_ctx_set_trace(self._h, ctypes.c_void_p(trace.data_ptr()), int(trace.shape[0])))
         self._trace = trace
+
+    _plan_scratch = None   # launch_plan's device scratch (uint8) for _plan_rays rays, grown on demand
+    _plan_rays = 0
+
+    def launch_plan(self, nray, total, state, count, prev_work, work, order, row_slot, nslot):
+        """``rwrt_launch_plan`` on this context's scratch and the device's
+        current stream: fills ``work``, ``order``, ``row_slot``, ``nslot`` and
+        updates ``prev_work`` (device tensors); returns the number of live rays
+        (waits for the stream once)."""
+        lib = load()
+        if self._plan_scratch is None or self._plan_rays < nray:   # (asked once per size, not per launch)
+            need = _I64()
+            check(lib.rwrt_launch_plan_bytes(int(nray), ctypes.byref(need)))
+            self._plan_scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._plan_rays = int(nray)
+        n_live = _I64()
+        i64 = torch.int64
+        check(lib.rwrt_launch_plan(int(nray), PLAN_TOTAL if total else PLAN_SINCE, dptr(state), dptr(count, i64),
+                                   dptr(prev_work, i64), dptr(work, i64), dptr(order, i64),
+                                   dptr(row_slot, torch.int32), dptr(nslot, i64), ctypes.byref(n_live),
+                                   dptr(self._plan_scratch), self._plan_scratch.numel(), stream(self.device)))
+        return int(n_live.value)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

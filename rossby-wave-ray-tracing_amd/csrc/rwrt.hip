@@ -2550,6 +2550,19 @@ __device__ __forceinline__ void store_tail(double* tail_row, int64_t ray, double
   o[3] = r3;
 }
 
+// Where a tails call wants every ray's last row (d_tail_row; NULL: nowhere).
+// The address is not a kernel argument: it lies in the header in front of the
+// context's frozen-ray flags (frozen_flag_kernel writes it) and is fetched
+// only where a ray's state is written back, so that the ray loop holds no
+// register for it (a.frozen is live there anyway; launch_run always sets it).
+// As a kernel argument, or read through the kernarg segment pointer, it cost
+// the attempt blocks scalar spills (tools/hot_count.py).
+constexpr int kFlagHead = 256;   // bytes in front of the flags
+template <class BG>
+__device__ __forceinline__ double* last_rows(const RunArgs<BG>& a) {
+  return *reinterpret_cast<double* const*>(a.frozen - kFlagHead);
+}
+
 // rwrt_ctx_set_trace: where (HW_ID, XCC) and when a traced ray ran
 constexpr int kTraceWords = 10;
 __device__ __forceinline__ void trace_start(int64_t* tr, int64_t w) {
@@ -2991,7 +3004,14 @@ __device__ __forceinline__ void quad_run(const RunArgs<StaticBG>& a, const Cache
     cos_prev = cos_c;
     it = last;
     if (st == 2) t = a.tbound[a.it_end - 1];
-    if (it == a.it_end) break;
+    if (it == a.it_end) {
+      if (writer) {   // the ray's last row of the call (tails)
+        if (double* const lr = last_rows(a))
+          store_tail(lr, ray, make_double2(y[0], y[1]), make_double2(y[2], y[3]), make_double2(y[4], ug),
+                     make_double2(vg, (double)nacc));
+      }
+      break;
+    }
   }
   if (writer) {
 #pragma unroll
@@ -3222,6 +3242,8 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
     it = last;
     if (st == Lane<RayProblem, KStore>::kFrozen) L.t = a.tbound[a.it_end - 1];
     if (it == a.it_end && writer) {
+      // its last row of the call (tails), first: r0..r3 die here
+      if (double* const lr = last_rows(a)) store_tail(lr, ray, r0, r1, r2, r3);
 #pragma unroll
       for (int v = 0; v < 5; ++v) {
         a.state[v * a.nray + ray] = y[v];
@@ -3362,7 +3384,9 @@ rk45_run_kernel(RunArgs<BG> a) {
 // ---------------------------------------------------------------------------
 __global__ void frozen_flag_kernel(const double* __restrict__ state, int64_t nray,
                                    uint8_t* __restrict__ frozen, int32_t* __restrict__ tail_from = nullptr,
-                                   int32_t it_begin = 0, int32_t it_end = 0) {
+                                   int32_t it_begin = 0, int32_t it_end = 0, double* tail_row = nullptr) {
+  // (the header in front of the flags: where the run kernel stores last rows, last_rows)
+  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<double**>(frozen - kFlagHead) = tail_row;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nray;
        i += (int64_t)gridDim.x * blockDim.x) {
     double sum = state[i];
@@ -3961,7 +3985,8 @@ rwrt_status ctx_flags(rwrt_ctx* c, int64_t nray) {
     c->cap = 0;
   }
   const size_t cap = ((size_t)nray + 4095) & ~(size_t)4095;
-  if (hipMalloc(reinterpret_cast<void**>(&c->flags), cap) != hipSuccess)
+  // (kFlagHead bytes more: launch_run's flags lie behind a header, last_rows)
+  if (hipMalloc(reinterpret_cast<void**>(&c->flags), cap + kFlagHead) != hipSuccess)
     return fail(RWRT_ERR_HIP, "frozen-ray flag allocation failed%s");
   c->cap = cap;
   return RWRT_OK;
@@ -4100,10 +4125,10 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   // tails, the side stream stores their constant tail rows instead of
   // filling (frozen_tail_kernel).
   if (rwrt_status s = ctx_flags(ctx, nray)) return s;
-  a.frozen = ctx->flags;
+  a.frozen = ctx->flags + kFlagHead;
   if (rwrt_status s = ctx_begin(ctx, st, [&] {
         hipLaunchKernelGGL(frozen_flag_kernel, dim3(grid_for(nray, 256)), dim3(256), 0, st, d_state, nray,
-                           ctx->flags, d_tail_from, it_begin, it_end);
+                           ctx->flags + kFlagHead, d_tail_from, it_begin, it_end, d_tail_row);
       }))
     return s;
   if constexpr (std::is_same<BG, StaticBG>::value) {

@@ -50,6 +50,11 @@ class RunResult:
         return int(self.nacc.sum().item())
 
 
+# a tails launch stores every ray's last row in Tails.row (include/rwrt.h);
+# RWRT_LAST_ROWS=0: last_row gathers it from the launch's rows, as before (A/B)
+LAST_ROWS = os.environ.get("RWRT_LAST_ROWS", "1") != "0"
+
+
 class Tails:
     """The constant row tails of one ray-loop launch (``rwrt_rk45_run_tails``,
     include/rwrt.h): ray j's rows from ``frm[j]`` (int32, in [i0, i1]; i1 = no
@@ -68,7 +73,10 @@ class Tails:
         return t
 
     def last_row(self, view, i1):
-        """Each ray's last row of the launch ``[i0, i1)`` whose rows are ``view``."""
+        """Each ray's last row of the launch ``[i0, i1)`` whose rows are ``view``:
+        ``row`` itself -- the launch stores every ray's last row there."""
+        if LAST_ROWS:
+            return self.row
         return torch.where((self.frm < i1)[:, None], self.row, view[:, -1])
 
 
@@ -96,7 +104,10 @@ class Slots:
         return self.n
 
     def last_row(self, view, tails, i1):
-        """Each ray's last row of the launch ``[i0, i1)`` (row blocks ``view``)."""
+        """Each ray's last row of the launch ``[i0, i1)`` (row blocks ``view``):
+        ``tails.row`` itself, as ``Tails.last_row``."""
+        if LAST_ROWS:
+            return tails.row
         blk = view[self.slot.clamp(min=0).to(torch.int64), -1] if view.shape[0] else tails.row
         return torch.where((tails.frm < i1)[:, None], tails.row, blk)
 
@@ -134,6 +145,11 @@ class RayEngine:
     # with at most this many rays left once the queue is drained continues
     # them in the quad layout (0: off).  Schedule only.
     handoff = int(os.environ.get("RWRT_HANDOFF", "16"))
+    # one native call orders a launch (rwrt_launch_plan: work per ray, row
+    # slots, longest-first order, live count) for the policies "priority",
+    # "cost" and "total" with a fixed latency-mode size; False: the torch
+    # expressions it replaces (cost_order, Slots.compute, team_size; A/B)
+    use_plan = os.environ.get("RWRT_PLAN", "1") != "0"
 
     def __init__(self, fields, lon, lat, device=None):
         """``fields``: the reference stack ``[nlon(+1), nlat, 18]`` (numpy or tensor);
@@ -541,6 +557,23 @@ class RayEngine:
             return 0, 16
         return n_best, q_best
 
+    def team_fixed(self, team, n_live):
+        """``team_size`` for an int or a pair ``team`` when the order is the
+        launch plan's: its first ``n_live`` rays are the live ones, so the
+        first ``n <= n_live`` are live without a look at the state."""
+        if self.bg is not None and self.bg.fp32 == 2:   # (none for fp32 arithmetic)
+            return 0, 16
+        ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        n, q = (int(team[0]), int(team[1])) if isinstance(team, (tuple, list)) else (int(team), 16)
+        return min(n, (ncu // 2) * 4 * (1 if self.bg is not None else q), n_live), q
+
+    def plan_buffers(self, nray):
+        """What ``rwrt_launch_plan`` writes for ``nray`` rays: the work, the
+        order, and row slots for a launch that has none of its own."""
+        return {"work": torch.empty(nray, dtype=torch.int64, device=self.device),
+                "order": torch.empty(nray, dtype=torch.int64, device=self.device),
+                "slots": Slots(nray, self.device)}
+
     def run(self, st, p, tbound, it_begin, it_end, out, order=None, n_heavy=0, rays_per_wave=16, tails=None,
             slots=None):
         """Rows ``[it_begin, it_end)`` into ``out[nray, it_end-it_begin, 8]`` (async);
@@ -776,6 +809,7 @@ class RayEngine:
         self.launch_log = []   # per launch: rows, rays in latency mode (diagnostics)
         self.launch_handoffs = []   # per launch: rays handed off at the drain (device int32)
         self.launch_work = []
+        plan, own_prev = None, False   # (rwrt_launch_plan's outputs; prev_work is this call's own tensor)
         k = 0
         while k < len(bounds):
             i0, i1 = bounds[k]
@@ -793,26 +827,36 @@ class RayEngine:
                           flush=True)
             flat = bufs[k % len(bufs)].view(-1)
             view = flat[: nblk * (i1 - i0) * H.NOUT].view(nblk, i1 - i0, H.NOUT)
-            slots = None
-            if sbufs is not None:
-                slots = sbufs[k % len(sbufs)]
-                if k > 0:   # (the first launch's were computed above)
-                    slots.compute(st, self._stream())
-            work = None
-            if order_policy in ("cost", "priority", "cell", "total") and prev_work is not None:
-                # the previous launch's attempts per ray, or ("total") all of them so far
-                work = cnt.sum(1) - (0 if order_policy == "total" else prev_work)
+            slots = sbufs[k % len(sbufs)] if sbufs is not None else None
             # (a list: one latency-mode size per launch, the last repeated)
             tk = team[min(k, len(team) - 1)] if isinstance(team, list) else team
-            if order_policy in ("cost", "priority", "cell", "total") and prev_work is not None:
-                head = (self.team_capacity_tv() if self.bg is not None else self.team_capacity()) if tk else 0
-                order = (self.cost_cell_order(st, work, head=head)
-                         if order_policy == "cell" else self.cost_order(st, work))
-            n_heavy, qpw = self.team_size(tk, st, work, order, i1 - i0) if tk else (0, 16)
+            costed = order_policy in ("cost", "priority", "cell", "total") and prev_work is not None
+            work = None
+            if costed and self.use_plan and order_policy != "cell" and tk != "auto" and nray > 0:
+                # one native call (rwrt_launch_plan): the attempts per ray since
+                # the previous launch, or ("total") all of them so far, the row
+                # slots, the longest-first order and the live count
+                plan = plan or self.plan_buffers(nray)
+                if not own_prev:   # (updated in place: not the caller's tensor)
+                    prev_work, own_prev = prev_work.clone(), True
+                work, order = plan["work"], plan["order"]
+                ps = slots if slots is not None else plan["slots"]
+                ps.n = self.ctx.launch_plan(nray, order_policy == "total", st["state"], cnt, prev_work, work,
+                                            order, ps.slot, ps.n_dev)
+                n_heavy, qpw = self.team_fixed(tk, ps.n) if tk else (0, 16)
+            else:
+                if slots is not None and k > 0:   # (the first launch's were computed above)
+                    slots.compute(st, self._stream())
+                if costed:
+                    work = cnt.sum(1) - (0 if order_policy == "total" else prev_work)
+                    head = (self.team_capacity_tv() if self.bg is not None else self.team_capacity()) if tk else 0
+                    order = (self.cost_cell_order(st, work, head=head)
+                             if order_policy == "cell" else self.cost_order(st, work))
+                n_heavy, qpw = self.team_size(tk, st, work, order, i1 - i0) if tk else (0, 16)
+                prev_work, own_prev = cnt.sum(1), True
             self.launch_log.append({"rows": [int(i0), int(i1)], "n_heavy": int(n_heavy), "per_wave": int(qpw)})
             if os.environ.get("RWRT_DEBUG_TEAM"):
                 print(f"launch rows [{i0}, {i1}): n_heavy {n_heavy} at {qpw} per wave", flush=True)
-            prev_work = cnt.sum(1)
             tails = tbufs[k % len(bufs)]
             if events is not None:
                 e0, e1, es = self._event_pair()

@@ -368,17 +368,22 @@ def run_sharded(eng, y0, nt, tstep=7200.0, group=None, rank=None, world=None, pr
         if events is not None:
             e1.record(es)
             events.append((e0, e1))
-        cost = st["count"].sum(1)                        # attempts in the probe
         frozen = torch.isnan(st["state"][:5].sum(0))
-        idx = cost_partition(cost, frozen, rank, world)
-        local = eng.take(st, idx)
-        prow_local, ptails_local = prow[idx], None if ptails is None else ptails.take(idx)
+        if world == 1:   # (every ray, in ray order: the set itself, no split and no copy of it)
+            idx = torch.arange(nray, device=eng.device)
+            local, prow_local, ptails_local = st, prow, ptails
+        else:
+            cost = st["count"].sum(1)                    # attempts in the probe
+            idx = cost_partition(cost, frozen, rank, world)
+            local = eng.take(st, idx)
+            prow_local, ptails_local = prow[idx], None if ptails is None else ptails.take(idx)
     last = {}
 
     dense = {}
 
     def keep(i0, i1, rows, tails=None, slots=None):
-        # the endpoints need each ray's last row only: a frozen ray's is its tail
+        # the endpoints need each ray's last row only: with tails the launch
+        # itself has stored it (Tails.last_row)
         if slots is not None:
             last["row"] = slots.last_row(rows, tails, i1)
         else:
@@ -389,11 +394,12 @@ def run_sharded(eng, y0, nt, tstep=7200.0, group=None, rank=None, world=None, pr
     keep.takes_slots = True
 
     keep(1, 1 + npr, prow_local, ptails_local)
-    n_live_local = int((~frozen[idx]).sum().item())
+    n_live_local = int((~(frozen if world == 1 else frozen[idx])).sum().item())
     res = eng.advance(local, p, tb, 1 + npr, chunk=chunk, sink=keep, out=out, events=events,
                       group=group, order_policy=order_policy, first_chunk=list(lead),
                       n_live=int(summary[0]), n_live_local=n_live_local,
-                      prev_work=torch.zeros_like(cost[idx]), team=team, split=split)
+                      prev_work=torch.zeros(idx.numel(), dtype=torch.int64, device=eng.device), team=team,
+                      split=split)
     steps_local = int(local["count"][:, 0].sum().item())
     ends = cnts = None
     if gather:
