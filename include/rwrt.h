@@ -839,6 +839,58 @@ rwrt_status rwrt_rk45_run_tv_slots(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt
 rwrt_status rwrt_rhs_tv(const rwrt_grid* g, const rwrt_background* b, int64_t n,
                         const double* d_t, const double* d_y, double* d_dydt,
                         void* stream);
+/* Member stacks (additive members of ABI 5): rays through nmember STATIC basic
+ * states on one grid in one launch -- forty winters, the members of an
+ * ensemble, three pressure levels, one flow at several truncations.  Every
+ * ray lives in one member for its whole life (d_member[ray]); nothing is
+ * interpolated between members, and a ray's rows, counters and state are bit
+ * for bit what rwrt_rk45_init / rwrt_rk45_run{,_tails,_slots} give for that
+ * ray on that member alone, whatever the other rays, the queue order or the
+ * chunking.
+ *
+ * Layout: d_packed[nmember][ncol][nrow][12] fp64, member m at d_packed +
+ * m * member_stride doubles (16-byte aligned: member_stride even, at least
+ * ncol*nrow*12) -- a levels stack whose t0 / dt are ignored.  d_member[nray]
+ * (int32, device): 0 <= member < nmember is the caller's duty; the kernels
+ * clamp the index wherever it addresses memory, so a bad one reads a wrong
+ * member, never outside the stack.
+ *
+ * Limit: the ray loop keeps one cache image per member (6 KiB per 64 grid
+ * points, rebuilt per call in the context's scratch) and addresses all of them
+ * by 32-bit offsets from one base:
+ *   nmember * ceil(ncol*nrow / 64) * 6 KiB + 8 KiB <= 2^32
+ * (about 43 members at 0.25 degrees, thousands at 2.5 degrees); a larger
+ * stack is RWRT_ERR_ARG.
+ *
+ * What stacks do not have: the latency mode (there is no n_heavy), the
+ * drain-time hand-off (rwrt_ctx_set_handoff is ignored), the lean RHS tier
+ * (every launch runs the full tier; the results are the same bits), fp32
+ * member storage, time-varying members, RK4.
+ *
+ * The one run entry covers the three row layouts: d_row_slot, d_tail_from and
+ * d_tail_row may be NULL under the rules of rwrt_rk45_run, _tails and _slots
+ * (tails need both tail buffers; row slots need tails).  Every other argument
+ * is as in rwrt_rk45_init / rwrt_rk45_run.  RWRT_ERR_ARG, with a message and
+ * before any HIP call: a NULL grid or stack, nmember < 1, a member_stride too
+ * small or odd, the limit above, NULL d_packed or d_member with nray > 0, and
+ * every check of rwrt_rk45_run (NULL ctx, params, row window, buffers,
+ * alignment, slots without tails). */
+typedef struct {
+  const double* d_packed;    /* [nmember][ncol][nrow][12] fp64 */
+  int32_t nmember, reserved;
+  int64_t member_stride;     /* doubles between two members, >= ncol*nrow*12 */
+  const int32_t* d_member;   /* [nray]: 0 <= member < nmember, the caller's duty */
+} rwrt_stack;                /* 32 bytes */
+rwrt_status rwrt_rk45_init_stack(const rwrt_grid* g, const rwrt_stack* stack, int64_t nray,
+                                 const double* d_y0, const rwrt_params* p, double* d_state,
+                                 int64_t* d_count, int32_t* d_nanrow, int32_t* d_live,
+                                 int64_t* d_summary, void* stream);
+rwrt_status rwrt_rk45_run_stack(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_stack* stack,
+                                int64_t nray, const rwrt_params* p, const double* d_tbound,
+                                int32_t it_begin, int32_t it_end, const int64_t* d_order,
+                                double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
+                                const int32_t* d_row_slot, int32_t* d_tail_from, double* d_tail_row,
+                                int32_t* d_work, void* stream);
 /* Stepper known-answer tests: the same device stepper on the analytic ODEs of
  * the rkf45.py demos (rkf45.py:839-882), driven like rk45_simple_current
  * (rkf45.py:672-724).  kind: 0 dx/dt = 2t, 1 dx/dt = e^(0.1 t), 2 Lorenz

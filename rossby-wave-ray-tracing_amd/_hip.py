@@ -27,6 +27,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_sh_filter",
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
                "rwrt_rk45_run_tv_slots", "rwrt_rhs_tv",
+               "rwrt_rk45_init_stack", "rwrt_rk45_run_stack",
                "rwrt_kat_rk45", "rwrt_selftest_math", "rwrt_host_fill_rows")
 
 RWRT_OK, RWRT_ERR_ARG, RWRT_ERR_HIP, RWRT_SOLVER_FAILED = 0, 1, 2, 3
@@ -57,6 +58,16 @@ class Params(ctypes.Structure):
 class Background(ctypes.Structure):
     _fields_ = [("d_levels", ctypes.c_void_p), ("nlev", ctypes.c_int32), ("fp32", ctypes.c_int32),
                 ("t0", ctypes.c_double), ("dt", ctypes.c_double)]
+
+
+class Stack(ctypes.Structure):
+    """``rwrt_stack``: ``nmember`` static basic states ``[nmember][ncol][nrow][12]``
+    (fp64, ``member_stride`` doubles apart) and each ray's member (int32, device)."""
+    _fields_ = [("d_packed", ctypes.c_void_p), ("nmember", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("member_stride", ctypes.c_int64), ("d_member", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(Stack) == 32
 
 
 class DensityMap(ctypes.Structure):
@@ -188,6 +199,9 @@ def load():
                                    _P],
         "rwrt_rk45_run_tv_slots": [_P, G, B, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P],
+        "rwrt_rk45_init_stack": [G, ctypes.POINTER(Stack), _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
+        "rwrt_rk45_run_stack": [_P, G, ctypes.POINTER(Stack), _I64, Pr, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P,
+                                _P, _P, _P],
         "rwrt_ctx_create": [_I32, ctypes.POINTER(_P)],
         "rwrt_ctx_destroy": [_P],
         "rwrt_ctx_set_latency_density": [_P, _I32],

@@ -49,6 +49,7 @@ __device__ __forceinline__ bool rwrt_rare_sink(bool c) {
 #endif
 
 #include "ray_point.h"   // constants, NumPy semantics, the packed state and its lookup, Merc, order_roots
+#include "stack_image.h" // member stacks: image offsets and the 32-bit limit (shared with the host check)
 
 namespace rwrt {
 
@@ -548,6 +549,97 @@ template <class Fill>
 __device__ __forceinline__ void lookup_end(const CachedStaticBG& B, const CachedStaticBG::Pending& p,
                                            double g[11], Fill&& fill) {
   B.end(p, g, fill);
+}
+
+// ---------------------------------------------------------------------------
+// A member stack (include/rwrt.h rwrt_stack): nmember static basic states on
+// one grid, every ray in one of them for its whole life (member[ray]); nothing
+// is interpolated between members.  A ray's arithmetic is the static path's on
+// its own member: at(m) IS that member's StaticBG, and the ray loop's cached
+// form below reads the member's own cache image through CachedStaticBG's
+// slice, blend and refill.
+// ---------------------------------------------------------------------------
+// Code placement.  The four StackBG kernels add metadata, symbols and kernel
+// descriptors in front of .text, which moved every existing kernel of this
+// code object by 5 632 bytes; with identical instructions the C3 bench lost
+// 2 % (seven interleaved pairs: 234.3-237.1 ms before, 239.2-241.2 ms after),
+// the placement effect of profiles/r5/sched/placement.txt.  This unused
+// read-only block makes the shift a whole 2 MiB, so that every kernel keeps
+// its address modulo 2 MiB: five pairs 235.5-235.9 ms (one run 243.4) against
+// 234.6-236.1 ms.  A shift of 64 KiB recovered half of it (236.8-238.0 ms).
+// DESIGN.md section 21.  When a kernel is added to this file, llvm-readelf -S
+// on the device code object shows what is left of it: .text's address modulo
+// 0x200000 was 0x13f00 without the stack kernels.
+#ifndef RWRT_PLACEMENT_PAD
+#define RWRT_PLACEMENT_PAD 0x1FEA00
+#endif
+__device__ __attribute__((used)) static const char kPlacementPad[RWRT_PLACEMENT_PAD] = {1};
+
+struct StackBG {
+  static constexpr bool kTimeVarying = false;
+  Field F;                         // the grid; F.P: member 0
+  const char* img = nullptr;       // nmember cache images, stack_image_bytes apart (the run kernel's refills)
+  const int32_t* member = nullptr; // [nray]
+  int64_t member_stride = 0;       // doubles between two members
+  int32_t nmember = 1;
+  // (clamped wherever it addresses memory: a bad index reads a wrong member, never outside the stack)
+  __device__ __forceinline__ int32_t member_of(int64_t ray) const {
+    return stack_clamp_member(member[ray], nmember);
+  }
+  __device__ __forceinline__ StaticBG at(int32_t m) const {
+    StaticBG S{F};
+    S.F.P = F.P + (int64_t)m * member_stride;
+    return S;
+  }
+};
+// The background a direct read (no cache) of ray `ray` goes to: the launch's
+// own, or the ray's member of a stack
+template <class BG>
+__device__ __forceinline__ const BG& ray_bg(const BG& B, int64_t) {
+  return B;
+}
+__device__ __forceinline__ StaticBG ray_bg(const StackBG& B, int64_t ray) { return B.at(B.member_of(ray)); }
+
+// StackBG's per-lane cached form: CachedStaticBG's slice and keys (C.img: the
+// base of the whole image stack) and the byte offset of the image of the
+// member this lane's ray lives in, added to the four corner offsets of a
+// refill -- nothing per lookup.  pull() sets it when the lane takes a ray and
+// drops the held cell: the previous ray's cell may be this one's too, but in
+// another member.  Not derived from CachedStaticBG on purpose: run_rays'
+// drain-time hand-off copies a CachedStaticBG for the quad layout, which
+// would slice the member away.
+struct CachedStackBG {
+  static constexpr bool kTimeVarying = false;
+  CachedStaticBG C;
+  mutable unsigned moff;   // stack_member_offset of the lane's member (32 bits: stack_fits)
+  __device__ __forceinline__ void pull(const StackBG& B, int64_t ray) const {
+    moff = (unsigned)stack_member_offset((int64_t)C.F.W * C.F.H, B.member_of(ray));
+    C.key_x = C.key_y = ~0u;
+  }
+  __device__ __forceinline__ CachedStaticBG::Pending begin(double lon, double lat) const {
+    const Corners k = corners(C.F, py_mod_2pi(lon), lat);
+    const bool miss = k.key_x != C.key_x || k.key_y != C.key_y;
+    if (miss) {   // miss: refill the slice from the member's image
+      C.refill(stack_point_offset(k.pa) + moff, stack_point_offset(k.pb) + moff,
+               stack_point_offset(k.pc) + moff, stack_point_offset(k.pd) + moff);
+      C.key_x = k.key_x;
+      C.key_y = k.key_y;
+    }
+    return CachedStaticBG::Pending{k.wa, k.wb, k.wc, k.wd, false};   // (cell_ok: the lean tier's, none here)
+  }
+};
+__device__ __forceinline__ CachedStaticBG::Pending lookup_begin(const CachedStackBG& B, double lon,
+                                                                double lat, double) {
+  return B.begin(lon, lat);
+}
+__device__ __forceinline__ void lookup_end(const CachedStackBG& B,
+                                           const CachedStaticBG::Pending& p, double g[11]) {
+  B.C.end(p, g, [] {});
+}
+template <class Fill>
+__device__ __forceinline__ void lookup_end(const CachedStackBG& B, const CachedStaticBG::Pending& p,
+                                           double g[11], Fill&& fill) {
+  B.C.end(p, g, fill);
 }
 // (the other backgrounds: the independent work first)
 template <class BG, class Fill>
@@ -1111,6 +1203,14 @@ struct LaneBG<StaticBG> {
     asm volatile("" : "+s"(hi));   // a second base pair: chunks 4-5 address like chunks 0-3
     return CachedStaticBG{B.F, B.img, lds + wave * kCacheBytesPerWave, (const char*)(uintptr_t)hi,
                           (threadIdx.x & 63u) * 16u, ~0u, ~0u};
+  }
+};
+template <>
+struct LaneBG<StackBG> {
+  using type = CachedStackBG;
+  static constexpr int kLdsBytes = 4 * kCacheBytesPerWave;
+  __device__ static CachedStackBG make(const StackBG& B, char* lds) {
+    return CachedStackBG{LaneBG<StaticBG>::make(StaticBG{B.F, B.img}, lds), 0u};
   }
 };
 template <>
@@ -2478,8 +2578,16 @@ __global__ void rk45_init_kernel(InitArgs<BG> a) {
     double y[5], f[5];
 #pragma unroll
     for (int v = 0; v < 5; ++v) y[v] = a.y0[v * a.nray + i];
-    P(0.0, y, f);                                   // RungeKutta.__init__: f = fun(t, y)
-    const double habs = initial_step(P, 0.0, y, f, a.rtol, a.atol);
+    double habs;
+    if constexpr (std::is_same<BG, StackBG>::value) {   // the static problem on the ray's own member
+      (void)P;
+      const RayProblemT<StaticBG> Pm{ray_bg(a.B, i)};
+      Pm(0.0, y, f);
+      habs = initial_step(Pm, 0.0, y, f, a.rtol, a.atol);
+    } else {
+      P(0.0, y, f);                                   // RungeKutta.__init__: f = fun(t, y)
+      habs = initial_step(P, 0.0, y, f, a.rtol, a.atol);
+    }
 #pragma unroll
     for (int v = 0; v < 5; ++v) {
       a.state[v * a.nray + i] = y[v];
@@ -3142,6 +3250,8 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
         ray = -1;
         continue;
       }
+      // (a member stack: the lane's lookups now go to this ray's member)
+      if constexpr (std::is_same<LBG, CachedStackBG>::value) P.B.pull(a.B, ray);
 #pragma unroll
       for (int v = 0; v < 5; ++v) {
         L.y[v] = a.state[v * a.nray + ray];
@@ -3210,7 +3320,7 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
       ug = L.aux[0];
       vg = L.aux[1];
     } else if (RARE(true)) {   // the last evaluation at y was masked (rare)
-      ugvg_at(a.B, tb, y[0], y[1], y[2], y[3], ug, vg);
+      ugvg_at(ray_bg(a.B, ray), tb, y[0], y[1], y[2], y[3], ug, vg);
     }
     const double2 r0 = make_double2(y[0], y[1]), r1 = make_double2(y[2], y[3]);
     const double2 r2 = make_double2(y[4], ug), r3 = make_double2(vg, (double)nacc);
@@ -3460,7 +3570,7 @@ __device__ __forceinline__ void frozen_row(const RunArgs<BG>& a, int64_t ray, do
       for (int v = 0; v < 5; ++v) y[v] = kNaN;
       ug = vg = kNaN;
     } else {
-      ugvg_at(a.B, tb, y[0], y[1], y[2], y[3], ug, vg);
+      ugvg_at(ray_bg(a.B, ray), tb, y[0], y[1], y[2], y[3], ug, vg);
     }
     r0 = make_double2(y[0], y[1]);
     r1 = make_double2(y[2], y[3]);
@@ -3942,6 +4052,7 @@ struct rwrt_ctx {
   int device = 0;
   int ncu = 256;
   int blocks_static = 0, blocks_f32 = 0, blocks_f64 = 0, blocks_a32 = 0;   // persistent grids
+  int blocks_stack = 0;
   uint8_t* flags = nullptr;
   size_t cap = 0;
   char* img = nullptr;         // cache image of the static state (cache_image_kernel), rebuilt per call
@@ -4021,11 +4132,45 @@ rwrt_status ctx_image(rwrt_ctx* c, const Field& F, hipStream_t stream, const cha
   return check_launch("cache_image_kernel");
 }
 
+// The cache images of a member stack for this call (as ctx_image: rebuilt
+// every call, on `stream`): cache_image_kernel once per member, member m's
+// image at stack_member_offset -- the layout CachedStackBG's refill addresses.
+// (The exponent range behind the images is the kernel's by-product: stacks
+// have no lean tier.)
+rwrt_status ctx_stack_images(rwrt_ctx* c, const StackBG& B, hipStream_t stream, const char** out) {
+  const int64_t npts = (int64_t)B.F.W * B.F.H;
+  const size_t image = (size_t)stack_image_bytes(npts);
+  const size_t need = image * (size_t)B.nmember + kRangeInts * sizeof(int);
+  if (need > c->img_cap) {
+    if (c->img) {
+      if ((c->used && hipEventSynchronize(c->done) != hipSuccess) || hipFree(c->img) != hipSuccess)
+        return check_launch("releasing the context's cache image");
+      c->img = nullptr;
+      c->img_cap = 0;
+    }
+    if (hipMalloc(reinterpret_cast<void**>(&c->img), need) != hipSuccess)
+      return fail(RWRT_ERR_HIP, "cache image allocation for the member stack failed%s");
+    c->img_cap = need;
+  }
+  int* r = reinterpret_cast<int*>(c->img + image * (size_t)B.nmember);
+  if (hipMemsetAsync(r, 0, kRangeInts * sizeof(int), stream) != hipSuccess)
+    return check_launch("hipMemsetAsync(exponent range)");
+  for (int32_t m = 0; m < B.nmember; ++m) {
+    Field F = B.F;
+    F.P = B.F.P + (int64_t)m * B.member_stride;
+    hipLaunchKernelGGL(cache_image_kernel, dim3(grid_for(npts * 6, 256)), dim3(256), 0, stream, F,
+                       c->img + stack_member_offset(npts, m), r);
+  }
+  *out = c->img;
+  return check_launch("cache_image_kernel (member stack)");
+}
+
 template <class BG> int& ctx_blocks(rwrt_ctx* c);
 template <> int& ctx_blocks<StaticBG>(rwrt_ctx* c) { return c->blocks_static; }
 template <> int& ctx_blocks<VaryingBG<float>>(rwrt_ctx* c) { return c->blocks_f32; }
 template <> int& ctx_blocks<VaryingBG<double>>(rwrt_ctx* c) { return c->blocks_f64; }
 template <> int& ctx_blocks<VaryingBGA32>(rwrt_ctx* c) { return c->blocks_a32; }
+template <> int& ctx_blocks<StackBG>(rwrt_ctx* c) { return c->blocks_stack; }
 
 template <class BG>
 int ctx_persistent_blocks(rwrt_ctx* c) {
@@ -4134,6 +4279,9 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   if constexpr (std::is_same<BG, StaticBG>::value) {
     if (rwrt_status s = ctx_image(ctx, B.F, st, &a.B.img, &a.B.range)) return s;
   }
+  if constexpr (std::is_same<BG, StackBG>::value) {
+    if (rwrt_status s = ctx_stack_images(ctx, B, st, &a.B.img)) return s;
+  }
   // latency mode in the run kernel's first team_blocks blocks (quad_rays):
   // one grid, so they are placed beside the persistent blocks whatever the
   // hardware queues' dispatch order (a second kernel on another stream could
@@ -4189,6 +4337,29 @@ rwrt_status make_varying(const rwrt_grid* g, const rwrt_background* b, VaryingBG
   B.t0 = b->t0;
   B.dt = b->dt;
   B.half = 0;
+  return RWRT_OK;
+}
+
+// a member stack from the ABI description: every check that needs no HIP call
+rwrt_status make_stack(const rwrt_grid* g, const rwrt_stack* s, int64_t nray, StackBG& B) {
+  if (!g) return fail(RWRT_ERR_ARG, "grid is NULL%s");
+  if (!s) return fail(RWRT_ERR_ARG, "stack is NULL%s");
+  if (s->nmember < 1) return fail(RWRT_ERR_ARG, "stack needs nmember >= 1%s");
+  const int64_t npts = (int64_t)g->ncol * g->nrow;
+  if (s->member_stride < npts * kNF || s->member_stride % 2 != 0)
+    return fail(RWRT_ERR_ARG, "member_stride must be even and at least ncol*nrow*12 doubles%s");
+  if (!stack_fits(npts, s->nmember))
+    return fail(RWRT_ERR_ARG,
+                "stack too large: nmember cache images (6 KiB per 64 grid points each) + 8 KiB must fit 32-bit "
+                "offsets (2^32 bytes)%s");
+  if (nray > 0 && !s->d_packed) return fail(RWRT_ERR_ARG, "stack d_packed is NULL%s");
+  if (nray > 0 && !s->d_member) return fail(RWRT_ERR_ARG, "stack d_member is NULL%s");
+  B = StackBG{};
+  if (s->d_packed)
+    if (rwrt_status st = make_field(g, s->d_packed, B.F)) return st;
+  B.member = s->d_member;
+  B.member_stride = s->member_stride;
+  B.nmember = s->nmember;
   return RWRT_OK;
 }
 
@@ -4771,6 +4942,27 @@ rwrt_status rwrt_rk45_run_tv_slots(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt
   if (!d_row_slot) return fail(RWRT_ERR_ARG, "rwrt_rk45_run_tv_slots needs d_row_slot%s");
   return run_tv(ctx, g, b, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count, d_nanrow,
                 d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
+}
+
+rwrt_status rwrt_rk45_init_stack(const rwrt_grid* g, const rwrt_stack* stack, int64_t nray,
+                                 const double* d_y0, const rwrt_params* p, double* d_state,
+                                 int64_t* d_count, int32_t* d_nanrow, int32_t* d_live,
+                                 int64_t* d_summary, void* stream) {
+  StackBG B;
+  if (rwrt_status s = make_stack(g, stack, nray, B)) return s;
+  return launch_init(B, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream);
+}
+
+rwrt_status rwrt_rk45_run_stack(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_stack* stack,
+                                int64_t nray, const rwrt_params* p, const double* d_tbound,
+                                int32_t it_begin, int32_t it_end, const int64_t* d_order,
+                                double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
+                                const int32_t* d_row_slot, int32_t* d_tail_from, double* d_tail_row,
+                                int32_t* d_work, void* stream) {
+  StackBG B;
+  if (rwrt_status s = make_stack(g, stack, nray, B)) return s;
+  return launch_run(ctx, B, nray, p, d_tbound, it_begin, it_end, d_order, 0, d_state, d_count, d_nanrow,
+                    d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
 }
 
 rwrt_status rwrt_rhs_tv(const rwrt_grid* g, const rwrt_background* b, int64_t n,

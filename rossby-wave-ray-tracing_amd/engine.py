@@ -170,6 +170,7 @@ class RayEngine:
         self.work = torch.zeros(4, dtype=torch.int32, device=self.device)
 
     bg = None   # rwrt_background of a time-varying state (None: the reference's static state)
+    nmember = 0  # members of a member-stack engine (from_levels(members=True)); 0: not one
     split_rho = None   # the last advance()'s rank correlation of its leading launches (split="auto")
     launch_log = ()    # the last advance()'s launches: rows and latency-mode decision
     rows_bytes = 0     # the last advance()'s row buffers (device bytes)
@@ -204,19 +205,33 @@ class RayEngine:
         return cls(bs.fields, bs.lon, bs.lat, device)
 
     @classmethod
-    def from_levels(cls, levels, time_varying=None):
+    def from_levels(cls, levels, time_varying=None, members=False):
         """Engine over a ``levels.Levels`` basic state.  One fp64 level is the
         reference's static state (same kernels, same bits); otherwise the
         time-varying kernels (``rwrt_rk45_*_tv``) run.  ``time_varying=True``
         sends one fp64 level through the time-varying kernels too (the test
-        that they reduce to the reference: tests/test_gpu_ref90.py)."""
+        that they reduce to the reference: tests/test_gpu_ref90.py).
+
+        ``members=True``: a member-stack engine (``rwrt_rk45_*_stack``) --
+        every level is one static basic state (``t0`` / ``dt`` ignored), every
+        ray lives in the member ``init`` / ``integrate`` are given for it
+        (``member=``), and its rows, counters and state are the static
+        engine's on that member bit for bit.  fp64 levels only; no latency
+        mode (``team``), process ``group``, RK4 or checkpoints."""
         self = cls.__new__(cls)
         self.device = levels.device
         self.grid = levels.grid
         self.lon, self.lat = levels.lon, levels.lat
         self.levels = levels
         self.work = torch.zeros(4, dtype=torch.int32, device=self.device)
-        if levels.nlev == 1 and not levels.fp32 and not time_varying:
+        if members:
+            if levels.fp32:
+                raise NotImplementedError("member stacks need fp64 level storage")
+            if time_varying:
+                raise ValueError("a member stack is static: members=True excludes time_varying=True")
+            self.packed, self.bg = None, None
+            self.nmember = int(levels.nlev)
+        elif levels.nlev == 1 and not levels.fp32 and not time_varying:
             self.packed = levels.packed[0]
             self.bg = None
         else:
@@ -306,15 +321,17 @@ class RayEngine:
     def zwn_tensor(self, zwn, freq):
         return torch.as_tensor(self.zwn_constants(zwn, freq), dtype=F64).to(self.device)
 
-    def initial_rows_dev(self, src, zc, rows=None, info=None):
+    def initial_rows_dev(self, src, zc, rows=None, info=None, packed=None):
         """Launch rwrt_ray_initial on resident inputs (``sources``, ``zwn_tensor``);
-        returns ``(rows[7, 3, nsource, nzwn], info[1])`` without synchronising."""
+        returns ``(rows[7, 3, nsource, nzwn], info[1])`` without synchronising.
+        ``packed``: the state to read (a member of a stack); default: the engine's."""
         ns, nz = src.shape[1], zc.shape[1]
         if rows is None:
             rows = torch.empty((7, 3, ns, nz), dtype=F64, device=self.device)
         if info is None:
             info = torch.zeros(1, dtype=torch.int32, device=self.device)
-        packed = self.packed if self.bg is None else self.levels.level0_f64   # the t = 0 state
+        if packed is None:
+            packed = self.packed if self.bg is None else self.levels.level0_f64   # the t = 0 state
         H.check(H.load().rwrt_ray_initial(self.grid, H.dptr(packed), ns, H.dptr(src[0]),
                                           H.dptr(src[1]), H.dptr(src[2]), nz, H.dptr(zc),
                                           H.dptr(rows), H.dptr(info), self._stream()))
@@ -326,9 +343,16 @@ class RayEngine:
         to the host path (np.roots restated in csrc/nproots.h); the source
         ``cos(lat)`` comes from the host libm, as in the reference.  With
         ``check`` (default), non-finite dispersion coefficients raise like
-        ``np.linalg.eigvals`` does in the reference."""
+        ``np.linalg.eigvals`` does in the reference.  A member-stack engine
+        returns ``rows[nmember, 7, 3, nsource, nzwn]``: the same call once per
+        member."""
         src = self.sources(source_lon, source_lat)
-        rows, info = self.initial_rows_dev(src, self.zwn_tensor(zwn, freq))
+        if self.nmember:
+            zc = self.zwn_tensor(zwn, freq)
+            per = [self.initial_rows_dev(src, zc, packed=self.levels.packed[m]) for m in range(self.nmember)]
+            rows, info = torch.stack([r for r, _ in per]), torch.stack([i for _, i in per]).sum(0)
+        else:
+            rows, info = self.initial_rows_dev(src, self.zwn_tensor(zwn, freq))
         if check and int(info.item()) != 0:
             raise np.linalg.LinAlgError(
                 f"Array must not contain infs or NaNs ({int(info.item())} dispersion "
@@ -403,10 +427,36 @@ class RayEngine:
         cut = cut_off * tstep / 3600.0 if cut_rad is None else float(cut_rad)   # wr.py:170
         return H.Params(rtol, atol, min_step, cut, int(nt), 0, tstep)
 
-    def init(self, y0, p):
-        """Solver construction on the GPU; returns the per-ray state tensors."""
+    def member_tensor(self, member, nray):
+        """The per-ray member indices of a stack engine as the int32 device
+        tensor the kernels read; ``ValueError`` for a wrong length or an index
+        outside ``[0, nmember)`` (checked on the host: the kernels only clamp)."""
+        if member is None:
+            raise ValueError("a member-stack engine needs member= (one index per ray)")
+        m = torch.as_tensor(member).to(self.device).reshape(-1)
+        if m.numel() != nray:
+            raise ValueError(f"member has {m.numel()} entries for {nray} rays")
+        if m.dtype.is_floating_point or m.dtype == torch.bool:
+            raise ValueError("member must be an integer tensor")
+        if nray and (int(m.min().item()) < 0 or int(m.max().item()) >= self.nmember):
+            raise ValueError(f"member index outside [0, {self.nmember})")
+        return m.to(torch.int32).contiguous()
+
+    def stack_of(self, st):
+        """The ``rwrt_stack`` of this engine's members for the rays of ``st``."""
+        pk = self.levels.packed
+        return H.Stack(H.dptr(pk, F64, "packed members"), self.nmember, 0, pk.stride(0),
+                       H.dptr(st["member"], torch.int32, "member"))
+
+    def init(self, y0, p, member=None):
+        """Solver construction on the GPU; returns the per-ray state tensors
+        (a member-stack engine: with each ray's ``member``, which ``take`` carries)."""
         y0 = torch.as_tensor(y0, dtype=F64, device=self.device).contiguous()
         nray = y0.shape[1]
+        if self.nmember:
+            member = self.member_tensor(member, nray)
+        elif member is not None:
+            raise ValueError("member= needs an engine built from_levels(members=True)")
         st = dict(
             state=torch.empty((H.NSTATE, nray), dtype=F64, device=self.device),
             count=torch.empty((nray, 2), dtype=torch.int64, device=self.device),
@@ -415,7 +465,11 @@ class RayEngine:
             summary=torch.zeros(2, dtype=torch.int64, device=self.device),
             nray=nray)
         lib = H.load()
-        if self.bg is None:
+        if self.nmember:
+            st["member"] = member
+            stack = self.stack_of(st)
+            fn, bg = lib.rwrt_rk45_init_stack, ctypes_ref(stack)
+        elif self.bg is None:
             fn, bg = lib.rwrt_rk45_init, H.dptr(self.packed)
         else:
             fn, bg = lib.rwrt_rk45_init_tv, ctypes_ref(self.bg)
@@ -589,6 +643,18 @@ class RayEngine:
         ctx.set_handoff(self.handoff)
         if slots is not None and tails is None:
             raise ValueError("row slots need tails")
+        if self.nmember:
+            # one entry for the three row layouts; no latency mode
+            if n_heavy:
+                raise ValueError("member stacks have no latency mode (n_heavy must be 0)")
+            stack = self.stack_of(st)
+            H.check(lib.rwrt_rk45_run_stack(
+                ctx.handle, self.grid, ctypes_ref(stack), st["nray"], ctypes_ref(p), H.dptr(tbound, F64),
+                int(it_begin), int(it_end), H.dptr(order, torch.int64), H.dptr(st["state"]), H.dptr(st["count"]),
+                H.dptr(st["nanrow"]), H.dptr(out, F64), None if slots is None else H.dptr(slots.slot, torch.int32),
+                None if tails is None else H.dptr(tails.frm, torch.int32),
+                None if tails is None else H.dptr(tails.row, F64), H.dptr(self.work), self._stream()))
+            return
         if self.bg is None:
             fn, bg = (lib.rwrt_rk45_run if tails is None else lib.rwrt_rk45_run_tails if slots is None
                       else lib.rwrt_rk45_run_slots), H.dptr(self.packed)
@@ -623,7 +689,7 @@ class RayEngine:
         stage input was masked (the ray keeps its state, wr.py:609-618; a masked
         first stage holds it for every remaining step, each counted).
         """
-        if self.bg is not None:
+        if self.bg is not None or self.nmember:
             raise NotImplementedError("the RK4 loop runs on the reference's static basic state")
         p = self.params(nt, tstep, cut_off=cut_off, cut_rad=cut_rad)
         y0 = torch.as_tensor(y0, dtype=F64, device=self.device).contiguous()
@@ -663,8 +729,14 @@ class RayEngine:
 
     def integrate(self, y0, nt, tstep, rtol=1e-6, atol=1e-6, msf=1e-3, cut_off=0.1,
                   ttotal=None, chunk=None, sink=None, out=None, cut_rad=None, events=None,
-                  group=None, order_policy="priority", first_chunk=None, team=0, stop_row=None):
+                  group=None, order_policy="priority", first_chunk=None, team=0, stop_row=None, member=None):
         """The whole ray loop for ``y0[5, nray]``; rows 1..nt-1 go to ``sink``.
+
+        ``member`` (a member-stack engine, ``from_levels(members=True)``): the
+        member each ray lives in, ``[nray]`` integers in ``[0, nmember)``; such
+        an engine takes ``team=0`` only and no ``group``, and its two global
+        outcomes (``failed``, ``break_row``) are over all rays of the call --
+        ``ensemble.member_outcomes`` decides them per member.
 
         ``sink(i0, i1, rows)`` receives each time chunk as a device tensor
         ``rows[nray, i1-i0, 8]`` (lon lat k l amp ug vg nacc) before the next
@@ -684,8 +756,12 @@ class RayEngine:
         p = self.params(nt, tstep, rtol, atol, msf, cut_off, cut_rad)
         y0 = torch.as_tensor(y0, dtype=F64, device=self.device).contiguous()
         nray = y0.shape[1]
+        if self.nmember:
+            self._check_stack_run(team, group)
+            if stop_row is not None:
+                raise NotImplementedError("member stacks have no checkpoints (stop_row)")
         tb = torch.as_tensor(t_eval_of(nt, tstep, ttotal), dtype=F64, device=self.device)
-        st = self.init(y0, p)
+        st = self.init(y0, p, member)
         summary = st["summary"]
         n_live_local = int(summary[0].item())   # this rank's shard (the queue bound)
         if group is not None:
@@ -764,6 +840,12 @@ class RayEngine:
         longest-first by the attempts since; otherwise live rays go first.
         ``split`` ("auto", see SPLIT_RHO) may split the launch after the
         leading ones once more."""
+        if self.nmember:
+            self._check_stack_run(team, group)
+            if "member" not in st:
+                raise ValueError("a member-stack engine advances a state of its own init (st['member'])")
+            if stop_row is not None:
+                raise NotImplementedError("member stacks have no checkpoints (stop_row)")
         nt = int(p.nt)
         end = nt if stop_row is None else max(int(start), min(int(stop_row), nt))
         nray = st["nray"]
@@ -886,6 +968,13 @@ class RayEngine:
         res.params = run_params(p, tb)
         return res
 
+    def _check_stack_run(self, team, group):
+        """What a member-stack engine's ray loop does not have, refused before any launch."""
+        if isinstance(team, (list, tuple)) or team != 0:
+            raise ValueError("member stacks have no latency mode: team must be 0")
+        if group is not None:
+            raise NotImplementedError("member stacks are not sharded over a process group")
+
     # ------------------------------------------------------ checkpoint / resume
     CHECKPOINT_KEYS = {"state", "count", "nanrow", "next_row", "params", "nray"}
 
@@ -898,6 +987,8 @@ class RayEngine:
         cut-off, nt, tstep, last output time) and ray count, which ``resume``
         checks."""
         st = res.state
+        if "member" in st:
+            raise NotImplementedError("member stacks have no checkpoints")
         return {"state": st["state"].cpu().numpy(), "count": st["count"].cpu().numpy(),
                 "nanrow": st["nanrow"].cpu().numpy(), "next_row": np.int64(res.next_row),
                 "params": np.asarray(res.params, np.float64), "nray": np.int64(st["nray"])}
@@ -927,6 +1018,8 @@ class RayEngine:
         """Rows ``[ck['next_row'], nt)`` of the run a checkpoint was taken from
         (the same ``nt``, ``tstep`` and tolerances), into ``sink`` as in
         ``integrate``: the rows and counters equal an uninterrupted run's."""
+        if self.nmember:
+            raise NotImplementedError("member stacks have no checkpoints")
         p = self.params(nt, tstep, rtol, atol, msf, cut_off, cut_rad)
         tb = torch.as_tensor(t_eval_of(nt, tstep, ttotal), dtype=F64, device=self.device)
         nray = int(ck["state"].shape[1])
@@ -953,8 +1046,11 @@ class RayEngine:
     @staticmethod
     def take(st, idx):
         """The per-ray state of rays ``idx`` (a device index tensor): a shard."""
-        return dict(state=st["state"][:, idx].contiguous(), count=st["count"][idx].contiguous(),
-                    nanrow=st["nanrow"][idx].contiguous(), nray=int(idx.numel()))
+        sub = dict(state=st["state"][:, idx].contiguous(), count=st["count"][idx].contiguous(),
+                   nanrow=st["nanrow"][idx].contiguous(), nray=int(idx.numel()))
+        if "member" in st:   # (a member stack's rays keep their member)
+            sub["member"] = st["member"][idx].contiguous()
+        return sub
 
     @staticmethod
     def live_first_order_of(st):
