@@ -1,5 +1,5 @@
 // Stand-alone host program over csrc/arrival_rows.h (the per-ray walk the
-// arrival kernel uses), built by tests/test_arrival_host.py with
+// arrival kernel uses), built by tests/support/hostprog.py with
 // -fsanitize=undefined,address,float-cast-overflow -fno-sanitize-recover=all
 // and run directly.
 //
@@ -24,20 +24,12 @@
 #include <vector>
 
 #include "arrival_rows.h"
+#include "launch_input.h"
 
 namespace {
 
-double read_double() {
-  char s[64];
-  if (scanf("%63s", s) != 1) exit(2);
-  return strtod(s, nullptr);
-}
-
-int read_int() {
-  int v;
-  if (scanf("%d", &v) != 1) exit(2);
-  return v;
-}
+using host_input::read_double;
+using host_input::read_int;
 
 struct Arrays {
   std::vector<int32_t> first, last;
@@ -92,34 +84,13 @@ int main() {
   const int nlaunch = read_int();
   long long rays = 0;
   for (int q = 0; q < nlaunch; ++q) {
-    const int nray = read_int(), it_begin = read_int(), it_end = read_int();
-    const int has_tails = read_int(), has_slots = read_int(), nblock = read_int();
-    if (nray < 0 || it_begin < 0 || it_end <= it_begin || nblock < 0 || (has_slots && !has_tails)) return 2;
+    host_input::Launch in;
+    in.read();
+    const int nray = in.nray, it_begin = in.it_begin, it_end = in.it_end;
+    const std::vector<int32_t>& chan = in.chan;
+    if (it_begin < 0) return 2;
     if (m.window_rows > 0 && (long long)it_end > (long long)m.nwin * m.window_rows) return 2;
-    const int nrow = it_end - it_begin;
-    std::vector<int32_t> chan(nray), tail_from, slot;
-    std::vector<double> tail_row, rows;
-    for (int j = 0; j < nray; ++j) chan[j] = read_int();
-    if (has_tails) {
-      tail_from.resize(nray);
-      tail_row.resize((size_t)nray * RWRT_NOUT);
-      for (int j = 0; j < nray; ++j) tail_from[j] = read_int();
-      for (size_t k = 0; k < tail_row.size(); ++k) tail_row[k] = read_double();
-    }
-    if (has_slots) {
-      slot.resize(nray);
-      for (int j = 0; j < nray; ++j) {
-        slot[j] = read_int();
-        if (slot[j] < -1 || slot[j] >= nblock) return 2;
-      }
-    } else if (nblock != nray) {
-      return 2;
-    }
-    rows.resize((size_t)nblock * nrow * RWRT_NOUT);
-    for (size_t k = 0; k < rows.size(); ++k) rows[k] = read_double();
-    // (a launch without a block has an empty buffer: rows.data() may be NULL and is never read)
-    const rwrt::LaunchRows L{rows.data(), has_slots ? slot.data() : nullptr, has_tails ? tail_from.data() : nullptr,
-                             has_tails ? tail_row.data() : nullptr, it_begin, it_end};
+    const rwrt::LaunchRows L = in.rows();
     for (int j = 0; j < nray; ++j) {
       rwrt::arrival_ray<4>(L, j, chan[j], m, ew);
       // the same ray row by row, its tail expanded

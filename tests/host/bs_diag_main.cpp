@@ -1,5 +1,5 @@
 // Stand-alone host program over csrc/bs_diag.h (the per-node arithmetic the
-// kernels of rwrt_bs_diag use), built by tests/test_bsdiag_host.py with
+// kernels of rwrt_bs_diag use), built by tests/support/hostprog.py with
 // -fsanitize=undefined,address -fno-sanitize-recover=all and run directly.
 //
 // usage: bs_diag_main IN OUT

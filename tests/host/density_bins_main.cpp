@@ -1,5 +1,5 @@
 // Stand-alone host program over csrc/density_bins.h (the index function the
-// density kernel uses), built by tests/test_density_host.py with
+// density kernel uses), built by tests/support/hostprog.py with
 // -fsanitize=undefined,address,float-cast-overflow -fno-sanitize-recover=all
 // and run directly: a float -> integer conversion of an unchecked value, or
 // any other undefined behaviour in the index arithmetic, aborts the run.

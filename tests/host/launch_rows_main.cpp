@@ -1,5 +1,5 @@
 // Stand-alone host program over csrc/launch_rows.h (how the density and the
-// summary kernels read a launch's rows), built by tests/test_launch_rows_host.py
+// summary kernels read a launch's rows), built by tests/support/hostprog.py
 // with -fsanitize=undefined,address,float-cast-overflow
 // -fno-sanitize-recover=all and run directly.  Every array is a heap block of
 // exactly the size given, so a read through a missing row block, past the end

@@ -1,6 +1,6 @@
 // Stand-alone host program over csrc/shsf_legendre.h (the quadrature weights
 // and the Legendre recurrence of the spherical-harmonic filter), built by
-// tests/test_shsf_host.py with -fsanitize=undefined,address
+// tests/support/hostprog.py with -fsanitize=undefined,address
 // -fno-sanitize-recover=all and run directly.
 //
 // usage:  shsf_legendre_main NLAT TRUNC

@@ -1,5 +1,5 @@
 // Stand-alone host program over csrc/summary_rows.h (the per-row update the
-// summary kernel uses), built by tests/test_summary_host.py with
+// summary kernel uses), built by tests/support/hostprog.py with
 // -fsanitize=undefined,address,float-cast-overflow -fno-sanitize-recover=all
 // and run directly.
 //
@@ -21,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "launch_input.h"
 #include "summary_rows.h"
 
 namespace {
@@ -29,11 +30,7 @@ struct Row {
   double lon, lat, l, amp;
 };
 
-double read_double() {
-  char s[64];
-  if (scanf("%63s", s) != 1) exit(2);
-  return strtod(s, nullptr);
-}
+using host_input::read_double;
 
 unsigned long long bits(double x) {
   unsigned long long u;

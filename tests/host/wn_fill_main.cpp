@@ -1,5 +1,5 @@
 // Stand-alone host program over csrc/wn_fill.h (the per-entry arithmetic the
-// fill kernel uses), built by tests/test_wn_host.py with
+// fill kernel uses), built by tests/support/hostprog.py with
 // -fsanitize=undefined,address -fno-sanitize-recover=all and run directly.
 //
 // stdin:  nlon nlat nplane cyclic

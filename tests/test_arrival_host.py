@@ -5,9 +5,6 @@ stand-alone program under the sanitizers (crafted launches in all three row
 layouts), and the argument checks of ``rwrt_ray_arrival``."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,9 +13,11 @@ import _hip as H
 from arrival import INT32_MAX, ArrivalSpec, reference_arrival
 from conftest import golden
 from density import DensitySpec, reference_bins
-from test_density_host import corner_points, random_points, scalar_bin
+from support import hostprog
+from support.abi import refused
+from support.cases_density import corner_points, random_points, scalar_bin
+from support.rows import LAYOUTS, layout_text, no_block
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF, NAN = math.inf, math.nan
 
 
@@ -133,30 +132,8 @@ def test_reference_arrival_c1_history(nx, ny):
 
 
 # ------------------------------------------------ csrc/arrival_rows.h on the host
-def _build_host_program(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "arrival_rows_main")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-           "-fsanitize=undefined,address", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
-           "-o", exe, os.path.join(ROOT, "tests", "host", "arrival_rows_main.cpp")]
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    if b.returncode != 0 and "sanitize" in b.stderr and "arrival_rows" not in b.stderr:
-        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
-
-
-@pytest.fixture(scope="module")
-def host_program(tmp_path_factory):
-    return _build_host_program(tmp_path_factory.mktemp("arrival_host"))
-
-
+host_program = hostprog.fixture("arrival_rows")
 NRAY = 41
-SENTINEL = (1.0, 0.1, 5.0)   # finite, binnable: must never be counted
 
 
 def crafted_launch(i0, i1, seed, tf=None):
@@ -200,50 +177,13 @@ def crafted_launch(i0, i1, seed, tf=None):
     return dict(i0=i0, i1=i1, rows=rows, tail=tail, tf=tf, chan=chan)
 
 
-def launch_text(L, layout):
-    """The launch in one of the three row layouts, as the host program reads it."""
-    i0, i1, rows, tail, tf, chan = (L[k] for k in ("i0", "i1", "rows", "tail", "tf", "chan"))
-    nray = rows.shape[0]
-    hexrow = lambda r: " ".join(float(x).hex() for x in r)       # noqa: E731
-    out = []
-    buf = rows.copy()
-    if layout != "dense":
-        cut = np.clip(tf, i0, i1)
-        for j in range(nray):
-            buf[j, cut[j] - i0:] = 0.0
-            buf[j, cut[j] - i0:, 0], buf[j, cut[j] - i0:, 1], buf[j, cut[j] - i0:, 4] = SENTINEL
-    slot = None
-    if layout == "slots":
-        live = np.where(np.arange(nray) % 3 != 0)[0]
-        slot = np.full(nray, -1, np.int32)
-        slot[live] = np.random.default_rng(1).permutation(len(live))
-        blocks = np.empty((len(live),) + buf.shape[1:])
-        blocks[slot[live]] = buf[live]
-        buf = blocks
-    out.append(f"{nray} {i0} {i1} {int(layout != 'dense')} {int(layout == 'slots')} {buf.shape[0]}")
-    out.append(" ".join(str(int(c)) for c in chan))
-    if layout != "dense":
-        out.append(" ".join(str(int(t)) for t in tf))
-        out += [hexrow(tail[j]) for j in range(nray)]
-    if slot is not None:
-        out.append(" ".join(str(int(s)) for s in slot))
-    out += [hexrow(r) for r in buf.reshape(-1, 8)]
-    return out
-
-
 def run_host_program(exe, spec, launches, layout):
     c = spec.c_struct()
     lines = [f"{c.bins.nx} {c.bins.ny} {c.bins.nchan} {c.bins.wcol} {c.bins.inv_dlon.hex()} {c.bins.lat0.hex()} "
              f"{c.bins.inv_dlat.hex()} {c.window_rows} {c.nwin}", str(len(launches))]
     for L in launches:
-        lines += launch_text(L, layout)
-    # (verify_asan_link_order=0: the environment may preload a library of its own)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
-    out = r.stdout.splitlines()
+        lines += layout_text(L, layout)
+    out = hostprog.run(exe, lines)
     first = np.array(out[0].split(), np.int64)
     got = {"first": np.where(first == INT32_MAX, -1, first).astype(np.int32).reshape(spec.shape),
            "last": np.array(out[1].split(), np.int32).reshape(spec.shape), "count": None}
@@ -282,7 +222,7 @@ def test_walk_host_program_under_sanitizers(host_program, window_rows, require):
     assert (want["first"] >= 0).sum() > 20
     if window_rows == 2:
         assert spec.nwin == 4 and (want["count"].sum(axis=(1, 2, 3)) > 0).all()   # a tail from row 1 spans 4 windows
-    for layout in ("dense", "tails", "slots"):
+    for layout in LAYOUTS:
         got, _ = run_host_program(host_program, spec, [L], layout)
         assert_same(got, want, layout)
 
@@ -298,7 +238,7 @@ def test_walk_host_program_launches_combine(host_program, layout):
              dict(whole, i0=4, i1=8, rows=whole["rows"][:, 3:])]
     if layout == "slots":                                               # (rays without a block: all tail)
         for p in [whole] + parts:
-            nob = np.arange(NRAY) % 3 == 0
+            nob = no_block(NRAY)
             p["tf"] = np.where(nob, p["i0"], p["tf"])
             p["rows"] = p["rows"].copy()
             p["rows"][nob] = p["tail"][nob, None]
@@ -383,9 +323,7 @@ def test_arrival_argument_errors_without_a_gpu():
         if word is None:
             assert _call(lib, nray=0, **kw) == H.RWRT_OK, kw
             continue
-        assert _call(lib, **kw) == H.RWRT_ERR_ARG, kw
-        assert word in lib.rwrt_last_error(), (kw, lib.rwrt_last_error())
-        assert lib.rwrt_last_error().startswith(b"rwrt_ray_arrival: ")
+        refused(lib, _call, kw, word, b"rwrt_ray_arrival: ")
     # no rays: a no-op (no device is touched; there is none on the build host)
     assert _call(lib, good, nray=0, rows=None) == H.RWRT_OK
     assert _call(lib, good, nray=0, rows=None, i1=9) == H.RWRT_OK                      # the last row of the last window

@@ -5,9 +5,6 @@ stand-alone program under the sanitizers (crafted launches in all three row
 layouts), and the argument checks of ``rwrt_ray_cross``."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,10 +13,13 @@ import _hip as H
 import cross as X
 from cross import CrossSpec, Gate, reference_cross
 from density import with_channels
-from test_arrival_host import launch_text
-from test_track_host import NRAY, c1_rows, crafted_history, launches_of, rows_of, sum_bound
+from support import hostprog
+from support.abi import refused
+from support.cases_cross import (C1_GATES, GATES8, VARIANTS, assert_c1, assert_crafted_is_rich, assert_cross, c1_spec,
+                                 crafted_spec, reference_and_abs)
+from support.cases_track import NRAY, c1_rows, crafted_history, launches_of, rows_of
+from support.rows import LAYOUTS, layout_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TWO_PI = 2 * math.pi
 INF, NAN = math.inf, math.nan
 
@@ -155,35 +155,6 @@ def test_spec():
             Gate(*bad)
 
 
-# ---------------------------------------------------- the reference's C1 history
-C1_GATES = (Gate.lat(30.0), Gate.lat(0.0), Gate.lon(180.0))
-C1_NORTH, C1_SOUTH = [0, 77, 55], [0, 78, 56]
-C1_WINDOWS = [23, 28, 27, 31, 31, 32, 33, 31, 30]
-C1_EAST = [0, 10, 8]
-
-
-def c1_spec(**kw):
-    return CrossSpec(C1_GATES, 36, window_rows=120, nt=1081, **kw)
-
-
-def assert_c1(r, what=""):
-    """The literals of the definition on the C1 history (3 roots, 1081 rows, by root)."""
-    cnt = r["cnt"]
-    assert cnt.shape == (9, 3, 2, 3, 36), what
-    g30 = cnt[:, 0]
-    assert g30.sum(axis=(0, 2, 3)).tolist() == [132, 134], what
-    assert g30.sum(axis=(0, 3)).tolist() == [C1_NORTH, C1_SOUTH], what
-    assert np.count_nonzero(g30.sum(axis=(0, 1, 2))) == 36, what
-    assert g30.sum(axis=(1, 2, 3)).tolist() == C1_WINDOWS, what
-    assert r["ncross"][0].tolist() == [C1_NORTH, C1_SOUTH], what
-    assert r["tfirst"][0, 1, 1] == 0.0 and np.isnan(r["tfirst"][0, :, 0]).all(), what   # the source lies on the gate
-    assert cnt[:, 1].sum() == 0 and r["ncross"][1].sum() == 0 and np.isnan(r["tfirst"][1]).all(), what
-    m180 = cnt[:, 2]
-    assert m180.sum(axis=(0, 3)).tolist() == [C1_EAST, [0, 0, 0]], what
-    assert np.count_nonzero(m180.sum(axis=(0, 1, 2))) == 4 and r["dropped"] == 0, what
-    assert r["ncross"][2].tolist() == [C1_EAST, [0, 0, 0]], what
-
-
 def test_reference_cross_c1_history():
     rows = c1_rows()
     r = reference_cross(rows, np.arange(3), c1_spec(nchan=3))
@@ -199,92 +170,8 @@ def test_reference_cross_c1_history():
     assert flat["wsum"][0, 0].sum() > 0 and r["wsum"] is None
 
 
-# ------------------------------------------------------------- crafted launches
-GATES8 = (Gate.lat(0.0), Gate.lon(0.0), Gate.lat(30.0), Gate.lon(90.0), Gate.lat(-20.0), Gate.lon(180.0),
-          Gate.lat(72.0), Gate.lon(270.0))
-VARIANTS = {
-    "8-gates-weight-windows": dict(gates=GATES8, weight="ug", window_rows=3),
-    "8-gates": dict(gates=GATES8),
-    "1-gate-weight": dict(gates=GATES8[:1], weight="vg", need=None),
-    "1-meridian-windows": dict(gates=GATES8[1:2], window_rows=3),
-    "3-gates-weight": dict(gates=GATES8[2:5], weight="k"),
-}
-
-
-def crafted_spec(name, nt, **kw):
-    v = dict(VARIANTS[name])
-    if v.get("window_rows"):
-        v["nt"] = nt
-    return CrossSpec(nbin=7, nchan=3, lat_range=(-60.0, 60.0), **{**v, **kw})
-
-
-def reference_and_abs(rows, chan, spec):
-    """``reference_cross`` and the per-bin sums of |tc| and |wv| (the sum|v| of
-    the rounding bound) in one pass over the crossings."""
-    rows = np.asarray(rows, np.float64)
-    want = reference_cross(rows, chan, spec)
-    a = np.zeros((2,) + spec.shape)
-    for x in X.crossings(rows, chan, spec):
-        if x is not None and x[5] >= 0:
-            g, d, j, c, w, b, t, tc, wv = x
-            a[0, w, g, d, c, b] += abs(tc)
-            a[1, w, g, d, c, b] += abs(wv)
-    return want, a
-
-
-def assert_cross(got, want, a=None, what="", per_ray=True):
-    """cnt, dropped and ncross exactly, tfirst bit for bit; tsum and wsum
-    exactly (``a`` None) or to the bound."""
-    assert got["cnt"].dtype == np.int64 and np.array_equal(got["cnt"], want["cnt"]), (what, "cnt")
-    assert int(got["dropped"]) == int(want["dropped"]), (what, "dropped", got["dropped"], want["dropped"])
-    if per_ray:
-        assert got["ncross"].dtype == np.int32 and np.array_equal(got["ncross"], want["ncross"]), (what, "ncross")
-        same = got["tfirst"].view(np.int64) == want["tfirst"].view(np.int64)
-        assert np.all(same | (np.isnan(got["tfirst"]) & np.isnan(want["tfirst"]))), (what, "tfirst")
-    for q, name in enumerate(("tsum", "wsum")):
-        if want[name] is None:
-            assert got[name] is None, (what, name)
-            continue
-        assert np.all(np.isfinite(got[name])), (what, name)
-        if a is None:
-            assert np.array_equal(got[name], want[name]), (what, name)
-        else:
-            err = np.abs(got[name] - want[name])
-            assert np.all(err <= sum_bound(want["cnt"], a[q])), (what, name, float(err.max()))
-
-
-def assert_crafted_is_rich(rows, chan, spec):
-    """More than 50 crossings, both directions on both kinds, a drop and a
-    meridian crossing outside lat_range: checked on the definition's side."""
-    xs = list(X.crossings(rows, chan, spec))
-    hits = [x for x in xs if x is not None]
-    kinds = {(spec.gates[x[0]].kind, x[1]) for x in hits}
-    assert len(hits) > 50 and xs.count(None) >= 1, (len(hits), xs.count(None))
-    assert kinds == {(k, d) for k in {g.kind for g in spec.gates} for d in (0, 1)}, kinds
-    if any(g.kind == 1 for g in spec.gates):
-        assert any(x[5] < 0 for x in hits if spec.gates[x[0]].kind == 1)
-
-
-def _build_host_program(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "cross_lines_main")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-           "-fsanitize=undefined,address", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
-           "-o", exe, os.path.join(ROOT, "tests", "host", "cross_lines_main.cpp")]
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    if b.returncode != 0 and "sanitize" in b.stderr and "cross_lines" not in b.stderr:
-        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
-
-
-@pytest.fixture(scope="module")
-def host_program(tmp_path_factory):
-    return _build_host_program(tmp_path_factory.mktemp("cross_host"))
+# ------------------------------------------- csrc/cross_lines.h on the host
+host_program = hostprog.fixture("cross_lines")
 
 
 def run_host_program(exe, spec, launches, nray=NRAY):
@@ -295,14 +182,8 @@ def run_host_program(exe, spec, launches, nray=NRAY):
         lines.append(f"{q.kind} " + " ".join(float(x).hex() for x in (q.pos, q.org, q.inv_d)))
     lines.append(str(len(launches)))
     for L, layout in launches:
-        lines += launch_text(L, layout)
-    # (verify_asan_link_order=0: the environment may preload a library of its own)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
-    out = r.stdout.splitlines()
+        lines += layout_text(L, layout)
+    out = hostprog.run(exe, lines)
     floats = lambda s: np.array([float.fromhex(x) if "nan" not in x else NAN for x in s.split()])   # noqa: E731
     cnt = np.array(out[0].split(), np.int64).reshape(spec.shape)
     tsum, wsum = floats(out[1]).reshape(spec.shape), floats(out[2]).reshape(spec.shape)
@@ -328,7 +209,7 @@ def test_lines_host_program_under_sanitizers(host_program, name):
     assert want["ncross"].sum() > 5
     off = ~((h["chan"] >= 0) & (h["chan"] < 3))
     assert off.any() and want["ncross"][:, :, off].sum() == 0
-    for layout in ("dense", "tails", "slots"):
+    for layout in LAYOUTS:
         got = run_host_program(host_program, spec, launches_of(h, [(1, 8)], layout))
         print(f"{name} {layout}: {want['ncross'].sum()} crossings, {want['cnt'].sum()} in the map, "
               f"{want['dropped']} dropped")
@@ -416,9 +297,7 @@ def test_cross_argument_errors_without_a_gpu():
         (dict(m=good, ncross=None), b"d_ncross"), (dict(m=good, tfirst=None), b"d_tfirst"),
     ]
     for kw, word in cases:
-        assert _call(lib, **kw) == H.RWRT_ERR_ARG, kw
-        assert word in lib.rwrt_last_error(), (kw, lib.rwrt_last_error())
-        assert lib.rwrt_last_error().startswith(b"rwrt_ray_cross: ")
+        refused(lib, _call, kw, word, b"rwrt_ray_cross: ")
     # the output pointers are checked with no rays too
     assert _call(lib, good, nray=0, rows=None, cnt=None) == H.RWRT_ERR_ARG
     # no rays: a no-op (no device is touched; there is none on the build host)

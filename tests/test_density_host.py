@@ -5,9 +5,6 @@ stand-alone program under the sanitizers, and the argument checks of
 ``rwrt_ray_density``."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,83 +12,9 @@ import pytest
 import _hip as H
 from conftest import golden
 from density import DensitySpec, bin_index, reference_bins
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TWO_PI = 2 * math.pi
-HALF_PI = math.pi / 2
-INF, NAN = math.inf, math.nan
-
-SPEC = DensitySpec(7, 5, nchan=2, weight="amp")     # 7 x 5 boxes of 51.4 x 36 degrees, two maps
-
-
-def corner_points():
-    """``(lon, lat, w, chan, expected)``: expected = (chan, iy, ix) written out
-    by hand, None for a point that is not binned."""
-    lat0, lat1 = -HALF_PI, HALF_PI
-    mid = 0.1          # (0.1 + pi/2) * 5/pi = 2.66 -> iy 2
-    pts = [
-        # longitudes (box width 2 pi / 7 = 0.8976 rad)
-        (0.0, mid, 1.0, 0, (0, 2, 0)),
-        (TWO_PI, mid, 1.0, 0, (0, 2, 0)),                       # 2 pi % 2 pi = 0
-        (-1e-20, mid, 1.0, 0, (0, 2, 0)),                       # % gives 2 pi, the second % gives 0
-        (math.nextafter(TWO_PI, 0.0), mid, 1.0, 0, (0, 2, 6)),  # the product floors to 7.0: clamped
-        (63.69, mid, 1.0, 0, (0, 2, 0)),                        # 63.69 - 10 * 2 pi = 0.858
-        (-5.0, mid, 1.0, 0, (0, 2, 1)),                         # 2 pi - 5 = 1.283
-        (3.2, mid, 1.0, 0, (0, 2, 3)),                          # 3.2 / 0.8976 = 3.57
-        # latitudes (box height pi / 5 = 0.6283 rad), map 1, lon 1.0 -> ix 1
-        (1.0, lat0, 1.0, 1, (1, 0, 1)),
-        # the last double below lat1: lat - lat0 rounds (to even) to pi itself, times 5/pi is 5.0 -> outside,
-        # as NumPy has it; two ulps further down the difference is below pi and the point is in the top row
-        (1.0, math.nextafter(lat1, 0.0), 1.0, 1, None),
-        (1.0, lat1 - 1e-9, 1.0, 1, (1, 4, 1)),
-        (1.0, lat1, 1.0, 1, None),                              # the upper edge is excluded
-        (1.0, math.nextafter(lat0, -INF), 1.0, 1, None),
-        (1.0, -0.3, 1.0, 1, (1, 2, 1)),                         # (-0.3 + pi/2) * 5/pi = 2.02
-        (1.0, -0.32, 1.0, 1, (1, 1, 1)),                        # 1.99
-        # non-finite and huge values
-        (NAN, mid, 1.0, 0, None), (INF, mid, 1.0, 0, None), (-INF, mid, 1.0, 0, None),
-        (1.0, NAN, 1.0, 0, None), (1.0, INF, 1.0, 0, None), (1.0, -INF, 1.0, 0, None),
-        (1.0, 1e300, 1.0, 0, None), (1.0, -1e300, 1.0, 0, None),
-        (1.0, mid, NAN, 0, None), (1.0, mid, INF, 0, None), (1.0, mid, -INF, 0, None),
-        (1.0, mid, 1e300, 0, (0, 2, 1)), (2.0, mid, -1e300, 0, (0, 2, 2)),   # finite weights count
-        # channels outside [0, nchan)
-        (1.0, mid, 1.0, -1, None), (1.0, mid, 1.0, 2, None),
-    ]
-    # a huge finite longitude is binned where Python's % puts it
-    for big in (1e300, -1e300):
-        lam = (big % TWO_PI) % TWO_PI
-        pts.append((big, mid, 1.0, 1, (1, 2, min(math.floor(lam * SPEC.inv_dlon), 6))))
-    return pts
-
-
-def scalar_bin(lon, lat, w, c, spec):
-    """The definition of the issue, point by point in Python floats."""
-    if not (math.isfinite(lon) and math.isfinite(lat)) or not 0 <= c < spec.nchan:
-        return None
-    if spec.wcol >= 0 and not math.isfinite(w):
-        return None
-    lam = (lon % TWO_PI) % TWO_PI
-    ix = min(math.floor(lam * spec.inv_dlon), spec.nx - 1)
-    fy = (lat - spec.lat0) * spec.inv_dlat
-    if not math.isfinite(fy) or not 0 <= math.floor(fy) < spec.ny:
-        return None
-    return (c, math.floor(fy), ix)
-
-
-def random_points(n, spec, seed=0):
-    rng = np.random.default_rng(seed)
-    lon = rng.uniform(-70.0, 70.0, n)
-    lat = rng.uniform(spec.lat0 - 0.2, spec.lat1 + 0.2, n)
-    w = rng.uniform(-2.0, 2.0, n)
-    chan = rng.integers(-1, spec.nchan + 1, n)
-    # some exactly on box edges, some non-finite
-    k = n // 10
-    lon[:k] = rng.integers(-20, 20, k) * (TWO_PI / spec.nx)
-    lat[k:2 * k] = spec.lat0 + rng.integers(-1, spec.ny + 2, k) * ((spec.lat1 - spec.lat0) / spec.ny)
-    lon[2 * k:2 * k + 20] = NAN
-    lat[2 * k + 20:2 * k + 40] = INF
-    w[2 * k + 40:2 * k + 60] = NAN
-    return lon, lat, w, chan
+from support import hostprog
+from support.abi import refused
+from support.cases_density import HALF_PI, INF, NAN, SPEC, TWO_PI, corner_points, random_points, scalar_bin
 
 
 def test_spec_factors():
@@ -162,23 +85,6 @@ def test_reference_bins_c1_history(nx, ny):
     assert np.array_equal(by_root.sum(0), count[0])
 
 
-def _build_host_program(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "density_bins_main")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-           "-fsanitize=undefined,address", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
-           "-o", exe, os.path.join(ROOT, "tests", "host", "density_bins_main.cpp")]
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    if b.returncode != 0 and "sanitize" in b.stderr and "density_bins" not in b.stderr:
-        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
-
-
 @pytest.mark.parametrize("spec", [SPEC, DensitySpec(1440, 720), DensitySpec(144, 72, lat_range=(-30, 60), nchan=3,
                                                                             weight="k")],
                          ids=["7x5", "1440x720", "144x72-band"])
@@ -187,7 +93,7 @@ def test_index_function_host_program_under_sanitizers(tmp_path, spec):
     built with ASan + UBSan + float-cast-overflow and run directly: the corner
     points and 10^5 random ones give reference_bins' indices, and the wrapped
     longitude equals Python's ``(lon % 2 pi) % 2 pi`` bit for bit."""
-    exe = _build_host_program(tmp_path)
+    exe = hostprog.build("density_bins", tmp_path)
     pts = corner_points()
     rl, rt, rw, rc = random_points(100000, spec, seed=11)
     lon = np.concatenate([[p[0] for p in pts], rl])
@@ -197,13 +103,7 @@ def test_index_function_host_program_under_sanitizers(tmp_path, spec):
     lines = [f"{spec.nx} {spec.ny} {spec.nchan} {spec.wcol} {spec.inv_dlon.hex()} {spec.lat0.hex()} "
              f"{spec.inv_dlat.hex()}"]
     lines += [f"{float(a).hex()} {float(b).hex()} {float(c).hex()} {int(d)}" for a, b, c, d in zip(lon, lat, w, chan)]
-    # (verify_asan_link_order=0: the environment may preload a library of its own)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
-    out = r.stdout.split()
+    out = hostprog.run_process(exe, lines).stdout.split()
     got = np.array(out[0::2], dtype=np.int64)
     lam = np.array([float.fromhex(x) if "nan" not in x else NAN for x in out[1::2]])
     assert len(got) == len(lon)
@@ -259,9 +159,7 @@ def test_density_argument_errors_without_a_gpu():
         (dict(m=good, wsum=64, rows=72), b"16-byte"), (dict(m=good, wsum=64, tfrom=64, trow=72), b"16-byte"),
     ]
     for kw, word in cases:
-        assert _call(lib, **kw) == H.RWRT_ERR_ARG, kw
-        assert word in lib.rwrt_last_error(), (kw, lib.rwrt_last_error())
-        assert lib.rwrt_last_error().startswith(b"rwrt_ray_density: ")
+        refused(lib, _call, kw, word, b"rwrt_ray_density: ")
     # no rays: a no-op (no device is touched; there is none on the build host)
     assert _call(lib, good, nray=0, rows=None, wsum=64) == H.RWRT_OK
     assert _call(lib, m(wcol=-1), nray=0, rows=None, wsum=None) == H.RWRT_OK

@@ -5,9 +5,6 @@ stand-alone program under the sanitizers (crafted launches in all three row
 layouts), and the argument checks of ``rwrt_ray_flux``."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,10 +14,13 @@ import flux as F
 from conftest import golden
 from density import DensitySpec, reference_bins
 from flux import FluxSpec, reference_flux
-from test_arrival_host import launch_text
-from test_density_host import corner_points, random_points
+from support import hostprog
+from support.abi import refused
+from support.cases_density import corner_points, random_points
+from support.cases_flux import (NRAY, VARIANTS, abs_sums, assert_flux, columns, crafted_launch, reference_of,
+                                sum_bound)
+from support.rows import LAYOUTS, layout_text, no_block
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TWO_PI = 2 * math.pi
 INF, NAN = math.inf, math.nan
 
@@ -72,49 +72,6 @@ def scalar_flux(lon, lat, k, l, ug, vg, chan, spec, row0=0):
             total[b + (1,)] += vy
             total[b + (2,)] += speed
     return {"count": count, "rowsum": rowsum, "sum": total}
-
-
-def abs_sums(lon, lat, k, l, ug, vg, chan, spec):
-    """Per bin and component the sum of |contribution| of the accepted points
-    (``[nchan, ny, nx, 3]``): the sum|v| of the rounding bound."""
-    chan = None if chan is None else np.asarray(chan, np.int64).reshape(-1, 1)
-    idx, vx, vy, sp = F.accept(lon, lat, k, l, ug, vg, chan, spec)
-    ok = idx >= 0
-    out = np.zeros((spec.nchan * spec.ny * spec.nx, 3))
-    for q, v in enumerate((vx, vy, sp)):
-        np.add.at(out[:, q], idx[ok], np.abs(np.broadcast_to(v, ok.shape)[ok]))
-    return out.reshape(spec.shape + (3,))
-
-
-def sum_bound(count, abs_sum):
-    """|got - ref| <= 2 (n + 1) 2^-53 sum|v| per bin and component: the bound
-    of a sum of n terms in any order, twice (both sides are rounded sums), plus
-    one rounding for a tail added as a product (tests/test_gpu_density.py)."""
-    return 2.0 * (count[..., None] + 1) * 2.0 ** -53 * abs_sum
-
-
-def assert_flux(got, want, abs_sum=None, what=""):
-    """count and rowsum exactly; the sums exactly (``abs_sum`` None) or to the bound."""
-    for name in ("count", "rowsum"):
-        assert got[name].dtype == np.int64 and np.array_equal(got[name], want[name]), (what, name)
-    if abs_sum is None:
-        assert np.array_equal(got["sum"], want["sum"]), (what, "sum")
-    else:
-        err = np.abs(got["sum"] - want["sum"])
-        assert np.all(err <= sum_bound(want["count"], abs_sum)), (what, "sum", float(err.max()))
-    assert np.all(np.isfinite(got["sum"])), what
-
-
-# the spec variants of the issue: wrapped and unwrapped, both vector kinds, finite filters
-VARIANTS = {
-    "wrapped": dict(),
-    "unit": dict(vector="unit"),
-    "three-circles": dict(lon_range=(-360.0, 720.0)),
-    "three-circles-unit": dict(lon_range=(-360.0, 720.0), vector="unit"),
-    "speed": dict(speed_range=(0.5, 2.5)),
-    "wn": dict(wn_max=2.0),
-    "all-filters-unit-window": dict(lon_range=(-720.0, 360.0), vector="unit", speed_range=(0.5, 3.5), wn_max=2.5),
-}
 
 
 def test_spec():
@@ -267,89 +224,7 @@ def test_reference_flux_c1_history_three_circles():
 
 
 # ------------------------------------------------ csrc/flux_rows.h on the host
-def _build_host_program(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "flux_rows_main")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-           "-fsanitize=undefined,address", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
-           "-o", exe, os.path.join(ROOT, "tests", "host", "flux_rows_main.cpp")]
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    if b.returncode != 0 and "sanitize" in b.stderr and "flux_rows" not in b.stderr:
-        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
-
-
-@pytest.fixture(scope="module")
-def host_program(tmp_path_factory):
-    return _build_host_program(tmp_path_factory.mktemp("flux_host"))
-
-
-NRAY = 41
-
-
-def crafted_launch(i0, i1, seed, tf=None, nray=NRAY):
-    """Logical rows ``[nray, i1 - i0, 8]`` of a launch ``[i0, i1)`` that all
-    three layouts can hold: ray j's rows from ``tf[j]`` on repeat its tail row.
-    ``tf`` runs through values below, at, inside, at the end of and above the
-    launch; the j % 3 == 0 rays (no row block in the slots layout) have at most
-    i0.  Longitudes span about three circles either side of 0; every fourth ray
-    drifts slowly (runs of several rows in one bin, going on into the tail),
-    the others jump from bin to bin; k, l in (-3, 3), speeds up to 4.2; NaN
-    and inf holes in lon, ug, vg, k and l, in rows and in tails; one ray at
-    rest; channels -1 and 3 among 0..2."""
-    rng = np.random.default_rng(seed)
-    nrow = i1 - i0
-    rows = rng.uniform(-3.0, 3.0, (nray, nrow, 8))
-    rows[..., 0] = rng.uniform(-20.0, 20.0, (nray, nrow))
-    rows[..., 1] = rng.uniform(-1.8, 1.8, (nray, nrow))
-    slow = np.arange(nray) % 4 == 1
-    rows[slow, :, 0] = rng.uniform(-6.0, 12.0, (slow.sum(), 1)) + 0.05 * np.arange(nrow)
-    rows[slow, :, 1] = rng.uniform(-1.0, 1.0, (slow.sum(), 1))
-    rows[3, nrow // 2, 5] = NAN                                  # holes in a run
-    rows[7, 0, 0] = INF
-    rows[9, nrow // 2, 6] = -INF
-    rows[13, 0, 2] = NAN
-    rows[17, nrow - 1, 3] = INF
-    rows[21, :, 5:7] = 0.0                                       # at rest while it is read
-    tail = rng.uniform(-3.0, 3.0, (nray, 8))
-    tail[:, 0] = rng.uniform(-20.0, 20.0, nray)
-    tail[:, 1] = rng.uniform(-1.8, 1.8, nray)
-    tail[5::7, 0] = NAN
-    tail[6::11, 5] = INF
-    tail[8::13, 3] = NAN
-    tail[:, 4] = NAN                                             # the amplitude is no criterion
-    if tf is None:
-        choice = sorted({i0 - 2, i0, i0 + 1, i0 + 3, i0 + 4, i0 + 5, i1 - 1, i1, i1 + 3})
-        j = np.arange(nray)
-        q = np.cumsum(j % 3 != 0)                                 # (the rays with a block take every value)
-        tf = np.where(j % 3 == 0, np.array([i0 - 2, i0])[(j // 3) % 2], np.array(choice)[q % len(choice)])
-    tf = np.asarray(tf, np.int32)
-    cut = np.clip(tf, i0, i1)
-    for j in range(nray):
-        rows[j, cut[j] - i0:] = tail[j]
-    # a slow ray whose tail continues its last bin: the run goes on into the tail
-    for j in np.where(slow)[0]:
-        if i0 < cut[j] < i1:
-            tail[j] = rows[j, cut[j] - i0 - 1]
-            rows[j, cut[j] - i0:] = tail[j]
-    chan = rng.integers(-1, 4, nray).astype(np.int32)            # -1 and nchan = 3 among them
-    return dict(i0=i0, i1=i1, rows=rows, tail=tail, tf=tf, chan=chan)
-
-
-def columns(rows):
-    return [rows[..., c] for c in (0, 1, 2, 3, 5, 6)]
-
-
-def reference_of(launches, spec):
-    """reference_flux of the launches' logical rows, summed; and their sum|v|."""
-    parts = [reference_flux(*columns(L["rows"]), L["chan"], spec, row0=L["i0"]) for L in launches]
-    want = {name: sum(p[name] for p in parts) for name in ("count", "rowsum", "sum")}
-    return want, sum(abs_sums(*columns(L["rows"]), L["chan"], spec) for L in launches)
+host_program = hostprog.fixture("flux_rows")
 
 
 def run_host_program(exe, spec, launches, layout):
@@ -358,14 +233,8 @@ def run_host_program(exe, spec, launches, layout):
         float(x).hex() for x in (c.lon0, c.inv_dlon, c.lat0, c.inv_dlat, c.s2_min, c.s2_max, c.wn_max)),
         str(len(launches))]
     for L in launches:
-        lines += launch_text(L, layout)
-    # (verify_asan_link_order=0: the environment may preload a library of its own)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
-    out = r.stdout.splitlines()
+        lines += layout_text(L, layout)
+    out = hostprog.run(exe, lines)
     cnt = np.array(out[0].split(), np.int64).reshape(spec.shape + (2,))
     total = np.array([float.fromhex(x) for x in out[1].split()]).reshape(spec.shape + (3,))
     emits = [int(x) for x in out[-1].split()[1:]]
@@ -388,7 +257,7 @@ def test_walk_host_program_under_sanitizers(host_program, name):
     want, a = reference_of([L], spec)
     total = int(np.isin(L["chan"], (0, 1, 2)).sum()) * 7
     assert 20 < want["count"].sum() < total and np.count_nonzero(want["count"]) > 10, want["count"].sum()
-    for layout in ("dense", "tails", "slots"):
+    for layout in LAYOUTS:
         got, emits = run_host_program(host_program, spec, [L], layout)
         assert_flux(got, want, a, (name, layout))
         assert emits[0] == emits[1] <= want["count"].sum()
@@ -404,7 +273,7 @@ def test_walk_host_program_launches_combine(host_program, layout):
              dict(whole, i0=4, i1=8, rows=whole["rows"][:, 3:])]
     if layout == "slots":                                               # (rays without a block: all tail)
         for p in [whole] + parts:
-            nob = np.arange(NRAY) % 3 == 0
+            nob = no_block(NRAY)
             p["tf"] = np.where(nob, p["i0"], p["tf"])
             p["rows"] = p["rows"].copy()
             p["rows"][nob] = p["tail"][nob, None]
@@ -481,9 +350,7 @@ def test_flux_argument_errors_without_a_gpu():
         (dict(m=good, cnt=None), b"d_cnt"), (dict(m=good, total=None), b"d_sum"),
     ]
     for kw, word in cases:
-        assert _call(lib, **kw) == H.RWRT_ERR_ARG, kw
-        assert word in lib.rwrt_last_error(), (kw, lib.rwrt_last_error())
-        assert lib.rwrt_last_error().startswith(b"rwrt_ray_flux: ")
+        refused(lib, _call, kw, word, b"rwrt_ray_flux: ")
     # the output pointers are checked with no rays too
     assert _call(lib, good, nray=0, rows=None, cnt=None) == H.RWRT_ERR_ARG
     # no rays: a no-op (no device is touched; there is none on the build host)

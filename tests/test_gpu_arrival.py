@@ -6,8 +6,6 @@ chunking and row layout, next to a ``DensitySink`` in one ``Tee``, across
 shards, through ``WR.ray_arrival`` on the reference's C1 history and on a
 time-varying background."""
 import math
-import os
-import socket
 
 import numpy as np
 import pytest
@@ -19,10 +17,10 @@ from conftest import golden
 from density import DensityMap, DensitySink, DensitySpec, bin_index
 from engine import Tails
 from summary import Tee
-from test_density_host import corner_points
-from test_gpu_density import (BOUNDARY_TF, I0, I1, NRAY, NT_C2, c1_wr, c2_chan, c2_ref, c2_wr, crafted, layouts,
-                              tv_engine)
-from test_gpu_parity import engine
+from support.cases import NT_C2, c1_wr, c2_chan, c2_ref, c2_wr, engine, tv_engine
+from support.cases_density import BOUNDARY_TF, I0, I1, NRAY, corner_points, crafted, launch
+from support.dist import one_rank
+from support.rows import SENTINEL, layout_device
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -64,7 +62,7 @@ def test_crafted_rows_every_layout(nx, ny, nchan, window_rows, boundary, require
     assert 0 < nbin < NRAY * (I1 - I0) and (want["first"] >= 0).sum() > 20
     assert want["first"][want["first"] >= 0].min() == I0 and want["last"].max() == I1 - 1
     dchan = torch.as_tensor(chan, device=DEV)
-    for name, (view, tails, slots) in layouts(rows, tail, tf).items():
+    for name, (view, tails, slots) in layout_device(launch(rows, tail, tf), SENTINEL).items():
         m = ArrivalMap(spec, DEV)
         m.add_rows(I0, I1, view, tails, slots, dchan)
         got = m.numpy()
@@ -301,58 +299,28 @@ def test_time_varying_background(fp32):
 
 
 # ------------------------------------------------------------- allreduce
-def _allreduce_worker(port, q):
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    sys.path[:0] = [os.path.join(root, "rossby-wave-ray-tracing_amd"), root, here]
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1)
-    try:
-        ops = []
-        f = dist.all_reduce
-        dist.all_reduce = lambda *a, **k: (ops.append(k.get("op")), f(*a, **k))[1]
-        from arrival import ArrivalMap, ArrivalSpec
-        rng = np.random.default_rng(0)
-        m = ArrivalMap(ArrivalSpec(144, 72, nt=9, window_rows=4), "cuda:0")
-        m.add_points(rng.uniform(0, 6.28, 5000), rng.uniform(-1.5, 1.5, 5000), rng.uniform(0, 2, 5000))
-        before = m.numpy()
-        m.allreduce(dist.group.WORLD)
-        after = m.numpy()
-        nops = len(ops)
-        names = [next((n for n in ("MIN", "MAX", "SUM") if o == getattr(dist.ReduceOp, n)), "?") for o in ops]
-        # WR.ray_arrival with a group, through the N-rank branches on one rank
-        # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does)
-        import shard
-        spec = ArrivalSpec(144, 72, nt=61, window_rows=12)
-        with np.errstate(all="ignore"):
-            alone = c2_wr().ray_arrival(spec, by="zwn").numpy()
-            shard.COLLECTIVE_MIN_WORLD = 1
-            grouped = c2_wr().ray_arrival(spec, by="zwn", group=dist.group.WORLD).numpy()
-        q.put(("ok", dist.get_backend(), names, before, after, alone, grouped, len(ops) - nops))
-    except Exception as e:  # pragma: no cover
-        q.put(("err", repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _allreduce_body(dist, ops):
+    rng = np.random.default_rng(0)
+    m = ArrivalMap(ArrivalSpec(144, 72, nt=9, window_rows=4), "cuda:0")
+    m.add_points(rng.uniform(0, 6.28, 5000), rng.uniform(-1.5, 1.5, 5000), rng.uniform(0, 2, 5000))
+    before = m.numpy()
+    m.allreduce(dist.group.WORLD)
+    after = m.numpy()
+    nops = len(ops)
+    names = [next((n for n in ("MIN", "MAX", "SUM") if o == getattr(dist.ReduceOp, n)), "?") for o in ops]
+    # WR.ray_arrival with a group, through the N-rank branches on one rank
+    # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does)
+    import shard
+    spec = ArrivalSpec(144, 72, nt=61, window_rows=12)
+    with np.errstate(all="ignore"):
+        alone = c2_wr().ray_arrival(spec, by="zwn").numpy()
+        shard.COLLECTIVE_MIN_WORLD = 1
+        grouped = c2_wr().ray_arrival(spec, by="zwn", group=dist.group.WORLD).numpy()
+    return dist.get_backend(), names, before, after, alone, grouped, len(ops) - nops
 
 
 def test_allreduce_one_rank_group_leaves_the_map_unchanged():
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_allreduce_worker, args=(port, q))
-    p.start()
-    res = q.get(timeout=120)
-    p.join(timeout=60)
-    assert res[0] == "ok", res
-    _, backend, names, before, after, alone, grouped, nops_wr = res
+    backend, names, before, after, alone, grouped, nops_wr = one_rank(_allreduce_body)
     assert backend == "nccl" and names == ["MIN", "MAX", "SUM"]
     assert before["count"].sum() == 5000 and before["count"][1:].sum() == 0
     assert_same(after, before, "one rank")

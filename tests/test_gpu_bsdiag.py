@@ -13,7 +13,8 @@ import torch
 
 import _hip as H
 from bsdiag import DIAG_NAMES, NEEDS_Q, BSDiag, reference_diag
-from test_bsdiag_host import ALL, axes, fixture, grid_steps, inputs, reference_of, same_bits
+from support.bits import bitwise as same_bits
+from support.cases_bsdiag import ALL, axes, fixture, grid_steps, inputs, reference_of
 
 pytestmark = pytest.mark.gpu
 

@@ -18,12 +18,12 @@ configs[2..4]) against the oracle.
   the oracle's TimeVaryingBackground.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
 
 from conftest import golden
+from support.dist import free_port
 
 pytestmark = pytest.mark.gpu
 C3_DAYS = 12
@@ -82,14 +82,6 @@ def test_c3_sample_bitwise_with_reference_arithmetic():
 
 
 # ---------------------------------------------------------------- C4
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _c4_worker(rank, world, port, q, shard_probe=False):
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -135,7 +127,7 @@ def test_c4_cost_sharded_world2_equals_single_gpu(shard_probe):
     hist, nacc, y0, bg, nt = c3_run()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_c4_worker, args=(r, 2, port, q, shard_probe)) for r in range(2)]
     for p in procs:
         p.start()

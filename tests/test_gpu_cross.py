@@ -8,8 +8,6 @@ to a ``DensitySink`` in one ``Tee``, across shards, through ``WR.ray_cross`` on
 the reference's C1 history, as the selection of a second integration, and on a
 time-varying background."""
 import math
-import os
-import socket
 
 import numpy as np
 import pytest
@@ -20,13 +18,12 @@ from cross import CrossMap, CrossSink, CrossSpec, Gate
 from density import DensityMap, DensitySink, DensitySpec, reference_bins
 from engine import Tails
 from summary import Tee
-from test_cross_host import (GATES8, VARIANTS, assert_c1, assert_cross, assert_crafted_is_rich, c1_spec,
-                             crafted_spec, reference_and_abs)
-from test_gpu_density import NT_C2, c1_wr, c2_chan, c2_wr, tv_engine
-from test_gpu_parity import engine
-from test_gpu_summary import c2_hist, c2_y0
-from test_gpu_track import device_layouts, start
-from test_track_host import assert_track, crafted_history
+from support.cases import NT_C2, c1_wr, c2_chan, c2_hist, c2_wr, c2_y0, engine, tv_engine
+from support.cases_cross import (GATES8, VARIANTS, assert_c1, assert_cross, assert_crafted_is_rich, c1_spec,
+                                 crafted_spec, reference_and_abs)
+from support.cases_track import assert_track, crafted_history, device_layouts, start
+from support.cases_track import reference_and_abs as track_reference_and_abs
+from support.dist import one_rank
 from track import TrackMap, TrackSink, TrackSpec
 
 pytestmark = pytest.mark.gpu
@@ -256,7 +253,6 @@ def test_crossed_selects_the_rays_of_a_second_integration():
     res = eng.integrate(y0[:, idx.cpu()].contiguous(), NT_C2, 7200.0, ttotal=(NT_C2 - 1) * 7200.0,
                         sink=TrackSink(tm).take(idx), chunk=60)
     chan = np.where(np.isin(np.arange(3072), sel), c2_chan(), -1)
-    from test_gpu_track import reference_and_abs as track_reference_and_abs
     twant, ta = track_reference_and_abs(c2_hist("zonal"), chan, tspec)
     assert twant["cnt"].sum() > 10000 and res is not None
     assert_track(tm.numpy(), twant, ta, "selected rays")
@@ -322,66 +318,36 @@ def test_time_varying_background():
 
 
 # ------------------------------------------------------------- allreduce
-def _allreduce_worker(port, q):
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    sys.path[:0] = [os.path.join(root, "rossby-wave-ray-tracing_amd"), root, here]
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1)
-    try:
-        ops = []
-        f = dist.all_reduce
-        dist.all_reduce = lambda *a, **k: (ops.append(k.get("op")), f(*a, **k))[1]
-        from cross import CrossMap, CrossSpec, Gate
-        rng = np.random.default_rng(0)
-        n = 2000
-        spec = CrossSpec((Gate.lat(0.0), Gate.lon(180.0)), 36, weight="ug")
-        rows = np.zeros((n, 2, 8))
-        rows[..., 0] = rng.uniform(0, 6.28, (n, 1)) + rng.uniform(-0.6, 0.6, (n, 2))
-        rows[..., 1] = rng.uniform(-0.3, 0.3, (n, 1)) + rng.uniform(-0.3, 0.3, (n, 2))
-        rows[..., 4], rows[..., 5] = 1.0, rng.uniform(-2, 2, (n, 2))
-        rows[0, 1, 0] = 1e300
-        m = CrossMap(spec, n, "cuda:0")
-        m.start(rows[:, 0, 0], rows[:, 0, 1], rows[:, 0, 4], rows[:, 0, 5])
-        m.add_rows(1, 2, torch.as_tensor(rows[:, 1:], device="cuda:0"))
-        before, prev = m.numpy(), m.prev.clone()
-        m.allreduce(dist.group.WORLD)
-        after = m.numpy()
-        same_prev = bool(torch.equal(prev, m.prev))
-        kinds = [str(o) for o in ops]
-        # WR.ray_cross with a group, through the N-rank branches on one rank
-        # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does)
-        import shard
-        wspec = CrossSpec((Gate.lat(25.0), Gate.lon(180.0)), 36, weight="amp")
-        with np.errstate(all="ignore"):
-            alone = c2_wr().ray_cross(wspec, by="zwn").numpy()
-            shard.COLLECTIVE_MIN_WORLD = 1
-            grouped = c2_wr().ray_cross(wspec, by="zwn", group=dist.group.WORLD).numpy()
-        q.put(("ok", dist.get_backend(), kinds, same_prev, before, after, alone, grouped, len(ops) - len(kinds)))
-    except Exception as e:  # pragma: no cover
-        q.put(("err", repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _allreduce_body(dist, ops):
+    rng = np.random.default_rng(0)
+    n = 2000
+    spec = CrossSpec((Gate.lat(0.0), Gate.lon(180.0)), 36, weight="ug")
+    rows = np.zeros((n, 2, 8))
+    rows[..., 0] = rng.uniform(0, 6.28, (n, 1)) + rng.uniform(-0.6, 0.6, (n, 2))
+    rows[..., 1] = rng.uniform(-0.3, 0.3, (n, 1)) + rng.uniform(-0.3, 0.3, (n, 2))
+    rows[..., 4], rows[..., 5] = 1.0, rng.uniform(-2, 2, (n, 2))
+    rows[0, 1, 0] = 1e300
+    m = CrossMap(spec, n, "cuda:0")
+    m.start(rows[:, 0, 0], rows[:, 0, 1], rows[:, 0, 4], rows[:, 0, 5])
+    m.add_rows(1, 2, torch.as_tensor(rows[:, 1:], device="cuda:0"))
+    before, prev = m.numpy(), m.prev.clone()
+    m.allreduce(dist.group.WORLD)
+    after = m.numpy()
+    same_prev = bool(torch.equal(prev, m.prev))
+    kinds = [str(o) for o in ops]
+    # WR.ray_cross with a group, through the N-rank branches on one rank
+    # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does)
+    import shard
+    wspec = CrossSpec((Gate.lat(25.0), Gate.lon(180.0)), 36, weight="amp")
+    with np.errstate(all="ignore"):
+        alone = c2_wr().ray_cross(wspec, by="zwn").numpy()
+        shard.COLLECTIVE_MIN_WORLD = 1
+        grouped = c2_wr().ray_cross(wspec, by="zwn", group=dist.group.WORLD).numpy()
+    return dist.get_backend(), kinds, same_prev, before, after, alone, grouped, len(ops) - len(kinds)
 
 
 def test_allreduce_one_rank_group_leaves_the_map_unchanged():
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_allreduce_worker, args=(port, q))
-    p.start()
-    res = q.get(timeout=120)
-    p.join(timeout=60)
-    assert res[0] == "ok", res
-    _, backend, kinds, same_prev, before, after, alone, grouped, nops_wr = res
+    backend, kinds, same_prev, before, after, alone, grouped, nops_wr = one_rank(_allreduce_body)
     assert backend == "nccl" and same_prev
     # cnt tsum wsum dropped ncross | tfirst
     assert len(kinds) == 6 and sum("SUM" in k for k in kinds) == 5 and "MIN" in kinds[-1]

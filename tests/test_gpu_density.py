@@ -6,8 +6,6 @@ through ``WR.ray_density`` on the reference's C1 history, on a time-varying
 background and across shards; the weighted sums within the rounding bound of
 a sum taken in any order."""
 import math
-import os
-import socket
 
 import numpy as np
 import pytest
@@ -16,83 +14,23 @@ import torch
 import synthetic as S
 from conftest import golden
 from density import DensityMap, DensitySink, DensitySpec, bin_index, reference_bins
-from engine import Slots, Tails
-from test_density_host import corner_points
-from test_gpu_parity import bs_of, engine, run_c2
+from engine import Tails
+from support.cases import C2_SPEC, NT_C2, c1_wr, c2_chan, c2_ref, c2_wr, engine, tv_engine
+from support.cases_density import BOUNDARY_TF, I0, I1, NRAY, corner_points, crafted, launch
+from support.dist import one_rank
+from support.rows import SENTINEL, layout_device
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-NT_C2 = 121          # 10 days
 
 
 # ------------------------------------------------- crafted rows, entry point
-NRAY, I0, I1 = 130, 1, 8     # three waves, the last partial; 7 rows
-SENTINEL = (1.0, 0.1, 5.0)   # finite, binnable: must never be counted
-
-
-def crafted(seed=0, tf=None):
-    """Logical rows ``[130, 7, 8]`` that all three layouts can hold: ray j's
-    rows from ``tf[j]`` on repeat its tail row; tf = it_begin / middle / it_end
-    by j % 3 (the j % 3 == 0 rays have no row block in the slots layout), or
-    the ``tf`` given, which may lie outside ``[I0, I1]`` (and is at most I0 for
-    those rays)."""
-    rng = np.random.default_rng(seed)
-    nrow = I1 - I0
-    rows = rng.uniform(-3.0, 3.0, (NRAY, nrow, 8))
-    rows[..., 0] = rng.uniform(-70.0, 70.0, (NRAY, nrow))
-    rows[..., 1] = rng.uniform(-1.8, 1.8, (NRAY, nrow))
-    pts = corner_points()
-    flat = rows.reshape(-1, 8)
-    where = rng.choice(flat.shape[0], len(pts), replace=False)
-    for k, p in zip(where, pts):
-        flat[k, 0], flat[k, 1], flat[k, 4] = p[0], p[1], p[2]
-    tail = rng.uniform(-3.0, 3.0, (NRAY, 8))
-    tail[:, 0] = rng.uniform(-70.0, 70.0, NRAY)
-    tail[:, 1] = rng.uniform(-1.8, 1.8, NRAY)
-    tail[5::7, 0] = np.nan                      # frozen NaN rays
-    tail[6::11, 4] = np.inf                     # a non-finite weight in a tail
-    tf = np.array([I0, I0 + 3, I1], np.int32)[np.arange(NRAY) % 3] if tf is None else np.asarray(tf, np.int32)
-    cut = np.clip(tf, I0, I1)
-    for j in range(NRAY):
-        rows[j, cut[j] - I0:] = tail[j]
-    return rows, tail, tf
-
-
-def layouts(rows, tail, tf, seed=1):
-    """``name -> (view, tails, slots)`` device objects of the same logical rows."""
-    rng = np.random.default_rng(seed)
-    nrow = I1 - I0
-    out = {"dense": (torch.as_tensor(rows, device=DEV).contiguous(), None, None)}
-    buf = rows.copy()
-    cut = np.clip(tf, I0, I1)
-    for j in range(NRAY):
-        buf[j, cut[j] - I0:] = 0.0
-        buf[j, cut[j] - I0:, 0], buf[j, cut[j] - I0:, 1], buf[j, cut[j] - I0:, 4] = SENTINEL
-    t = Tails(NRAY, DEV)
-    t.frm.copy_(torch.as_tensor(tf))
-    t.row.copy_(torch.as_tensor(tail))
-    out["tails"] = (torch.as_tensor(buf, device=DEV).contiguous(), t, None)
-    live = np.where(np.arange(NRAY) % 3 != 0)[0]
-    slot = np.full(NRAY, -1, np.int32)
-    slot[live] = rng.permutation(len(live)).astype(np.int32)
-    blocks = np.empty((len(live), nrow, 8))
-    blocks[slot[live]] = buf[live]
-    s = Slots(NRAY, DEV)
-    s.slot.copy_(torch.as_tensor(slot))
-    out["slots"] = (torch.as_tensor(blocks, device=DEV).contiguous(), t, s)
-    return out
-
-
 @pytest.mark.parametrize("spec,with_chan", [
     (DensitySpec(7, 5), False), (DensitySpec(7, 5, nchan=3, weight="amp"), True),
     (DensitySpec(1440, 720, weight="amp"), True), (DensitySpec(1440, 720, nchan=3), True)],
     ids=["7x5", "7x5x3-amp", "1440x720-amp", "1440x720x3"])
 def test_crafted_rows_every_layout(spec, with_chan):
     every_layout_equals_reference_bins(spec, with_chan, *crafted())
-
-
-# tail_from below, at and above the launch, and rows read on either side of the kernel's batch of 4
-BOUNDARY_TF = (I0 - 2, I0, I0 + 1, I0 + 3, I0 + 4, I0 + 5, I1, I1 + 3)
 
 
 @pytest.mark.parametrize("spec,with_chan", [(DensitySpec(7, 5, nchan=3, weight="amp"), True)], ids=["7x5x3-amp"])
@@ -116,7 +54,7 @@ def every_layout_equals_reference_bins(spec, with_chan, rows, tail, tf):
     abs_sum = None
     if spec.wcol >= 0:
         abs_sum = reference_bins(rows[..., 0], rows[..., 1], np.abs(rows[..., 4]), cref, spec)[1]
-    for name, (view, tails, slots) in layouts(rows, tail, tf).items():
+    for name, (view, tails, slots) in layout_device(launch(rows, tail, tf), SENTINEL).items():
         m = DensityMap(spec, DEV)
         m.add_rows(I0, I1, view, tails, slots, None if chan is None else torch.as_tensor(chan, device=DEV))
         count, wsum = m.numpy()
@@ -164,32 +102,6 @@ def test_add_points_is_row_zero():
 
 
 # ------------------------------------------------ C2 through the engine
-C2_SPEC = DensitySpec(360, 180, nchan=4, weight="amp")
-_C2 = {}
-
-
-def c2_chan():
-    return (np.arange(3 * 256 * 4) % 4).astype(np.int32)      # slot (root, source, zwn) -> zwn
-
-
-def c2_ref(method="rk45"):
-    """Dense rows of the 10-day C2 zonal run collected by a plain sink, and
-    their reference map (computed once)."""
-    if method not in _C2:
-        if method == "rk45":
-            hist, _ = run_c2("zonal", NT_C2)
-        else:
-            g = golden("init_C2_zonal.npz")
-            got = {}
-            engine("zonal").integrate_rk4(torch.as_tensor(g["rows"][:5].reshape(5, -1)), NT_C2, 7200.0,
-                                          sink=lambda a, b, o: got.__setitem__(a, o.cpu().numpy().copy()))
-            hist = np.concatenate([np.full((3072, 1, 8), np.nan)] + [got[k] for k in sorted(got)], axis=1)
-        pts = hist[:, 1:]
-        ref = reference_bins(pts[..., 0], pts[..., 1], pts[..., 4], c2_chan()[:, None], C2_SPEC)
-        _C2[method] = (pts, ref)
-    return _C2[method]
-
-
 def c2_density(spec=C2_SPEC, idx=None, rk4=False, **kw):
     g = golden("init_C2_zonal.npz")
     eng = engine("zonal")
@@ -281,17 +193,6 @@ def test_c2_additivity_over_shards():
 
 
 # ------------------------------------------------------- WR.ray_density (C1)
-def c1_wr():
-    from wr import WR
-    cfg = S.config("C1")
-    bs = bs_of("zonal")
-    wr = WR(cfg.nzwn, cfg.nsource, 7200.0, 90 * 86400.0, 0.0, nx=bs.nlon, ny=bs.nlat)
-    wr.bs = bs
-    wr.set_zwn(cfg.zwn)
-    wr.set_source_matrix(cfg.SW_lon, cfg.SW_lat, cfg.dlon, cfg.dlat, cfg.nnx, cfg.nny)
-    return wr
-
-
 def test_c1_ray_density_equals_the_reference_history():
     """C1, 90 days through WR.ray_density: the counts equal reference_bins of
     the reference's own golden history (rows 1..1080) plus row 0; by root,
@@ -332,21 +233,6 @@ def test_c1_ray_density_equals_the_reference_history():
 
 
 # ------------------------------------------------- time-varying background
-_TV = {}
-
-
-def tv_engine(fp32, nlev=5):
-    if fp32 not in _TV:
-        from engine import RayEngine
-        from levels import Levels
-        bl = [S.background_level(j) for j in range(nlev)]
-        lv = Levels(bl[0]["lat"], bl[0]["lon"], nlev, t0=0.0, dt=6 * 3600.0, fp32=fp32)
-        for j, b in enumerate(bl):
-            lv.set_level(j, b["u"], b["v"])
-        _TV[fp32] = RayEngine.from_levels(lv)
-    return _TV[fp32]
-
-
 @pytest.mark.parametrize("fp32", [False, True], ids=["fp64", "fp32-storage"])
 def test_time_varying_background(fp32):
     eng = tv_engine(fp32)
@@ -371,69 +257,28 @@ def test_time_varying_background(fp32):
 
 
 # ------------------------------------------------------------- allreduce
-def _allreduce_worker(port, q):
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    sys.path[:0] = [os.path.join(root, "rossby-wave-ray-tracing_amd"), root, here]
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1)
-    try:
-        calls = []
-        f = dist.all_reduce
-        dist.all_reduce = lambda *a, **k: (calls.append(1), f(*a, **k))[1]
-        from density import DensityMap, DensitySpec
-        rng = np.random.default_rng(0)
-        m = DensityMap(DensitySpec(144, 72, weight="amp"), "cuda:0")
-        m.add_points(rng.uniform(0, 6.28, 5000), rng.uniform(-1.5, 1.5, 5000), rng.uniform(0, 2, 5000))
-        before = m.numpy()
-        m.allreduce(dist.group.WORLD)
-        after = m.numpy()
-        ncalls = len(calls)
-        # WR.ray_density with a group, through the N-rank branches on one rank
-        # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does):
-        # the shard's sink, then the all-reduce of the map
-        import shard
-        spec = DensitySpec(144, 72, weight="amp")
-        with np.errstate(all="ignore"):
-            alone = c2_wr().ray_density(spec, by="zwn").numpy()
-            shard.COLLECTIVE_MIN_WORLD = 1
-            grouped = c2_wr().ray_density(spec, by="zwn", group=dist.group.WORLD).numpy()
-        q.put(("ok", dist.get_backend(), ncalls, before, after, alone, grouped, len(calls) - ncalls))
-    except Exception as e:  # pragma: no cover
-        q.put(("err", repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
-
-
-def c2_wr(nt=61):
-    from wr import WR
-    cfg = S.config("C2")
-    bs = bs_of("nonzonal")
-    w = WR(cfg.nzwn, cfg.nsource, 7200.0, (nt - 1) * 7200.0, cfg.freq, nx=bs.nlon, ny=bs.nlat, chunk_rows=20)
-    w.bs = bs
-    w.set_zwn(cfg.zwn)
-    w.set_source_matrix(cfg.SW_lon, cfg.SW_lat, cfg.dlon, cfg.dlat, cfg.nnx, cfg.nny)
-    return w
+def _allreduce_body(dist, calls):
+    rng = np.random.default_rng(0)
+    m = DensityMap(DensitySpec(144, 72, weight="amp"), "cuda:0")
+    m.add_points(rng.uniform(0, 6.28, 5000), rng.uniform(-1.5, 1.5, 5000), rng.uniform(0, 2, 5000))
+    before = m.numpy()
+    m.allreduce(dist.group.WORLD)
+    after = m.numpy()
+    ncalls = len(calls)
+    # WR.ray_density with a group, through the N-rank branches on one rank
+    # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does):
+    # the shard's sink, then the all-reduce of the map
+    import shard
+    spec = DensitySpec(144, 72, weight="amp")
+    with np.errstate(all="ignore"):
+        alone = c2_wr().ray_density(spec, by="zwn").numpy()
+        shard.COLLECTIVE_MIN_WORLD = 1
+        grouped = c2_wr().ray_density(spec, by="zwn", group=dist.group.WORLD).numpy()
+    return dist.get_backend(), ncalls, before, after, alone, grouped, len(calls) - ncalls
 
 
 def test_allreduce_one_rank_group_leaves_the_map_unchanged():
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_allreduce_worker, args=(port, q))
-    p.start()
-    res = q.get(timeout=120)
-    p.join(timeout=60)
-    assert res[0] == "ok", res
-    _, backend, ncalls, before, after, alone, grouped, ncalls_wr = res
+    backend, ncalls, before, after, alone, grouped, ncalls_wr = one_rank(_allreduce_body)
     assert backend == "nccl" and ncalls == 2
     assert before[0].sum() == 5000
     assert np.array_equal(before[0], after[0]) and np.array_equal(before[1], after[1])

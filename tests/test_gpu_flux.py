@@ -7,8 +7,6 @@ layout, next to a ``DensitySink`` in one ``Tee``, across shards, through
 ``WR.ray_flux`` on the reference's C1 history with and without a target
 region, and on a time-varying background."""
 import math
-import os
-import socket
 
 import numpy as np
 import pytest
@@ -18,42 +16,17 @@ import flux as F
 import synthetic as S
 from conftest import golden
 from density import DensityMap, DensitySink, DensitySpec
-from engine import Slots, Tails
+from engine import Tails
 from flux import FluxMap, FluxSink, FluxSpec, reference_flux
 from summary import RaySummary, Tee, reference_summary
-from test_flux_host import VARIANTS, abs_sums, assert_flux, columns, crafted_launch, reference_of, sum_bound
-from test_gpu_density import NT_C2, c1_wr, c2_chan, c2_ref, c2_wr, tv_engine
-from test_gpu_parity import engine
+from support.cases import NT_C2, c1_wr, c2_chan, c2_ref, c2_wr, engine, tv_engine
+from support.cases_flux import VARIANTS, abs_sums, assert_flux, columns, crafted_launch, reference_of, sum_bound
+from support.dist import one_rank
+from support.rows import layout_device
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-SENTINEL = (1.0, 0.1)     # lon lat of a row that must never be read: at rest, binnable, counted if it were
-
-
-# ------------------------------------------------- crafted rows, entry point
-def device_layouts(L, seed=1):
-    """``name -> (view, tails, slots)`` device objects of the launch's logical rows."""
-    i0, i1, rows, tail, tf = (L[k] for k in ("i0", "i1", "rows", "tail", "tf"))
-    nray, nrow = rows.shape[:2]
-    out = {"dense": (torch.as_tensor(rows, device=DEV).contiguous(), None, None)}
-    buf = rows.copy()
-    cut = np.clip(tf, i0, i1)
-    for j in range(nray):
-        buf[j, cut[j] - i0:] = 0.0
-        buf[j, cut[j] - i0:, 0], buf[j, cut[j] - i0:, 1] = SENTINEL
-    t = Tails(nray, DEV)
-    t.frm.copy_(torch.as_tensor(tf))
-    t.row.copy_(torch.as_tensor(tail))
-    out["tails"] = (torch.as_tensor(buf, device=DEV).contiguous(), t, None)
-    live = np.where(np.arange(nray) % 3 != 0)[0]
-    slot = np.full(nray, -1, np.int32)
-    slot[live] = np.random.default_rng(seed).permutation(len(live)).astype(np.int32)
-    blocks = np.empty((len(live), nrow, 8))
-    blocks[slot[live]] = buf[live]
-    s = Slots(nray, DEV)
-    s.slot.copy_(torch.as_tensor(slot))
-    out["slots"] = (torch.as_tensor(blocks, device=DEV).contiguous(), t, s)
-    return out
+SENTINEL = {0: 1.0, 1: 0.1}   # lon lat of a row that must never be read: at rest, binnable, counted if it were
 
 
 def scaled(m, factor):
@@ -77,7 +50,7 @@ def test_crafted_rows_every_layout(name, shape, nray):
     want, a = reference_of([L], spec)
     assert 20 < want["count"].sum() < nray * 7
     chan = torch.as_tensor(L["chan"], device=DEV)
-    for layout, (view, tails, slots) in device_layouts(L).items():
+    for layout, (view, tails, slots) in layout_device(L, SENTINEL).items():
         m = FluxMap(spec, DEV)
         m.add_rows(1, 8, view, tails, slots, chan)
         assert_flux(m.numpy(), want, a, (name, layout))
@@ -395,60 +368,30 @@ def test_time_varying_background():
 
 
 # ------------------------------------------------------------- allreduce
-def _allreduce_worker(port, q):
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    sys.path[:0] = [os.path.join(root, "rossby-wave-ray-tracing_amd"), root, here]
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1)
-    try:
-        ops = []
-        f = dist.all_reduce
-        dist.all_reduce = lambda *a, **k: (ops.append(k.get("op")), f(*a, **k))[1]
-        from flux import FluxMap, FluxSpec
-        rng = np.random.default_rng(0)
-        m = FluxMap(FluxSpec(144, 72), "cuda:0")
-        zero = np.zeros(5000)
-        m.add_points(rng.uniform(0, 6.28, 5000), rng.uniform(-1.5, 1.5, 5000), zero, zero,
-                     rng.uniform(-2, 2, 5000), rng.uniform(-2, 2, 5000))
-        before = m.numpy()
-        m.allreduce(dist.group.WORLD)
-        after = m.numpy()
-        nops = len(ops)
-        all_sum = all(o == dist.ReduceOp.SUM for o in ops)
-        # WR.ray_flux with a group, through the N-rank branches on one rank
-        # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does)
-        import shard
-        spec = FluxSpec(144, 72)
-        with np.errstate(all="ignore"):
-            alone = c2_wr().ray_flux(spec, by="zwn").numpy()
-            shard.COLLECTIVE_MIN_WORLD = 1
-            grouped = c2_wr().ray_flux(spec, by="zwn", group=dist.group.WORLD).numpy()
-        q.put(("ok", dist.get_backend(), nops, all_sum, before, after, alone, grouped, len(ops) - nops))
-    except Exception as e:  # pragma: no cover
-        q.put(("err", repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _allreduce_body(dist, ops):
+    rng = np.random.default_rng(0)
+    m = FluxMap(FluxSpec(144, 72), "cuda:0")
+    zero = np.zeros(5000)
+    m.add_points(rng.uniform(0, 6.28, 5000), rng.uniform(-1.5, 1.5, 5000), zero, zero,
+                 rng.uniform(-2, 2, 5000), rng.uniform(-2, 2, 5000))
+    before = m.numpy()
+    m.allreduce(dist.group.WORLD)
+    after = m.numpy()
+    nops = len(ops)
+    all_sum = all(o == dist.ReduceOp.SUM for o in ops)
+    # WR.ray_flux with a group, through the N-rank branches on one rank
+    # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does)
+    import shard
+    spec = FluxSpec(144, 72)
+    with np.errstate(all="ignore"):
+        alone = c2_wr().ray_flux(spec, by="zwn").numpy()
+        shard.COLLECTIVE_MIN_WORLD = 1
+        grouped = c2_wr().ray_flux(spec, by="zwn", group=dist.group.WORLD).numpy()
+    return dist.get_backend(), nops, all_sum, before, after, alone, grouped, len(ops) - nops
 
 
 def test_allreduce_one_rank_group_leaves_the_map_unchanged():
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_allreduce_worker, args=(port, q))
-    p.start()
-    res = q.get(timeout=120)
-    p.join(timeout=60)
-    assert res[0] == "ok", res
-    _, backend, nops, all_sum, before, after, alone, grouped, nops_wr = res
+    backend, nops, all_sum, before, after, alone, grouped, nops_wr = one_rank(_allreduce_body)
     assert backend == "nccl" and nops == 2 and all_sum
     assert before["count"].sum() == 5000 and before["rowsum"].sum() == 0
     assert_flux(after, before, None, "one rank")

@@ -79,7 +79,7 @@ def c3(request):
     first row at which it is frozen (from one dense launch; NT: never)."""
     from bench import make_bs
     from engine import RayEngine, t_eval_of
-    from test_gpu_tails import c3_sample_y0
+    from support.cases import c3_sample_y0
     bs, _ = make_bs(request.param)
     eng = RayEngine.from_bs(bs)
     y0 = c3_sample_y0(eng, n_dead=128)

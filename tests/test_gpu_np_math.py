@@ -31,7 +31,7 @@ def first_diff(got, want, x):
 
 def test_trig_on_device_equals_numpy():
     from engine import selftest_math as dev
-    from test_np_math import trig_args
+    from support.cases_npmath import trig_args
     x = trig_args(np.random.default_rng(11), 1 << 22)
     with np.errstate(all="ignore"):
         for name, ref in (("sin", np.sin), ("cos", np.cos), ("tan", np.tan)):

@@ -20,40 +20,12 @@ import torch
 
 from conftest import golden
 import synthetic as S
+from support.bits import bitwise, equal_nan
+from support.cases import bs_of, engine, run_c2, run_wr
 
 pytestmark = pytest.mark.gpu
 
 KINDS = ["zonal", "nonzonal"]
-_ENG = {}
-
-
-def bs_of(kind):
-    from bs import BS
-    bg = S.background(kind)
-    bs = BS(len(bg["lon"]), len(bg["lat"]))
-    bs.load_arrays(**bg)
-    bs.ready(xcyclic=True)
-    return bs
-
-
-def engine(kind):
-    if kind not in _ENG:
-        from engine import RayEngine
-        _ENG[kind] = RayEngine.from_bs(bs_of(kind))
-    return _ENG[kind]
-
-
-def ulps(a, b):
-    """Distance in units of the last place of max(|a|, |b|) (NaN == NaN -> 0)."""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    nan_a, nan_b = np.isnan(a), np.isnan(b)
-    assert np.array_equal(nan_a, nan_b), "NaN pattern differs"
-    a, b = np.where(nan_a, 0, a), np.where(nan_b, 0, b)
-    scale = np.spacing(np.maximum(np.abs(a), np.abs(b)))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        d = np.abs(a - b) / scale
-    d[(a == b)] = 0
-    return d
 
 
 def test_library_is_the_hip_build():
@@ -103,19 +75,7 @@ def test_initial_step(kind):
     assert live.sum() == int(st["summary"][0])
 
 
-def bitwise(a, b):
-    """Equal bit for bit (signed zeros distinguished; NaN == NaN)."""
-    a = np.where(np.isnan(a), np.nan, np.asarray(a, np.float64))
-    b = np.where(np.isnan(b), np.nan, np.asarray(b, np.float64))
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
 # ------------------------------------------------------------ initial rays
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
-
-
 @pytest.mark.parametrize("kind", KINDS)
 def test_initial_rows_gpu_bitwise_c2(kind):
     """rwrt_ray_initial (Mercator point, np.roots restated, change_roots_order,
@@ -126,7 +86,7 @@ def test_initial_rows_gpu_bitwise_c2(kind):
     w = WR(cfg.nzwn, cfg.nsource, 7200.0, 7200.0, cfg.freq, nx=144, ny=73)
     w.set_source_matrix(cfg.SW_lon, cfg.SW_lat, cfg.dlon, cfg.dlat, cfg.nnx, cfg.nny)
     rows = engine(kind).initial_rows(w.source_lon, w.source_lat, cfg.zwn, cfg.freq)
-    assert same_bits(rows.cpu().numpy(), g["rows"])
+    assert equal_nan(rows.cpu().numpy(), g["rows"])
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -139,7 +99,7 @@ def test_initial_rows_gpu_bitwise_c3_golden(kind):
         src = g[f"{tag}_{kind}_src"]
         rows = engine(kind).initial_rows(src[0], src[1], cfg.zwn, float(g[f"{tag}_{kind}_freq"]))
         got = rows.cpu().numpy()[[3, 4, 5, 6]]
-        assert same_bits(got, g[f"{tag}_{kind}_rows"]), tag
+        assert equal_nan(got, g[f"{tag}_{kind}_rows"]), tag
 
 
 @pytest.mark.refhost
@@ -163,25 +123,6 @@ def test_initial_rows_gpu_equals_host_full_c3(kind):
 
 
 # ------------------------------------------------------------------- T2 / T3
-def run_c2(kind, nt, chunk=None, order=None, eng=None, **kw):
-    from engine import t_eval_of
-    g = golden(f"init_C2_{kind}.npz")
-    eng = eng or engine(kind)
-    y0 = torch.as_tensor(g["rows"][:5].reshape(5, -1))
-    rows = {}
-
-    def sink(i0, i1, out):
-        rows[(i0, i1)] = out.cpu().numpy().copy()
-
-    res = eng.integrate(y0, nt, 7200.0, ttotal=(nt - 1) * 7200.0, chunk=chunk, sink=sink, **kw)
-    nray = y0.shape[1]
-    hist = np.full((nray, nt, 8), np.nan)
-    hist[:, 0, :7] = g["rows"].reshape(7, -1).T
-    for (i0, i1), r in rows.items():
-        hist[:, i0:i1] = r
-    return hist, res
-
-
 @pytest.mark.parametrize("kind", KINDS)
 def test_t2_c2_trajectories(kind):
     """C2 (3 072 slots) against the reference's own rows at 2 h, 1 d and 10 d
@@ -402,19 +343,6 @@ def test_jump_verdict_fast_path_near_threshold():
 
 
 # ------------------------------------------------------------------- RK4 mode
-def run_wr(kind, cfg_name, nt, inte_method):
-    from wr import WR
-    cfg = S.config(cfg_name)
-    bs = bs_of(kind)
-    w = WR(cfg.nzwn, cfg.nsource, 7200.0, (nt - 1) * 7200.0, cfg.freq, nx=bs.nlon, ny=bs.nlat)
-    w.bs = bs
-    w.set_zwn(cfg.zwn)
-    w.set_source_matrix(cfg.SW_lon, cfg.SW_lat, cfg.dlon, cfg.dlat, cfg.nnx, cfg.nny)
-    with np.errstate(all="ignore"):
-        w.ray_run(mode="hip", inte_method=inte_method)
-    return np.array([w.rlon, w.rlat, w.rzwn, w.rmwn, w.ramp, w.rug, w.rvg]).reshape(7, nt, -1)
-
-
 @pytest.mark.parametrize("kind", KINDS)
 def test_rk4_c2_bitwise(kind):
     """The reference's default integrator, RK4: C2 rows at the reference's

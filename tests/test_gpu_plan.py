@@ -115,7 +115,7 @@ def c3_257():
     from bench import make_bs
     from conftest import golden
     from engine import RayEngine
-    from test_gpu_tails import c3_sample_y0
+    from support.cases import c3_sample_y0
     bs, _ = make_bs("zonal")
     eng = RayEngine.from_bs(bs)
     y0 = c3_sample_y0(eng, n_dead=64)

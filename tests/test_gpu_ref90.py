@@ -40,7 +40,7 @@ def check_rows(got_sha, want_sha, hist, last):
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_rk45_c2_90d_bitwise_with_reference_arithmetic(kind):
-    from test_gpu_parity import run_c2
+    from support.cases import run_c2
     g = golden(f"ref90_C2_{kind}.npz")
     nt = int(g["nt"])
     hist, res = run_c2(kind, nt)
@@ -51,7 +51,7 @@ def test_rk45_c2_90d_bitwise_with_reference_arithmetic(kind):
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_rk4_c2_90d_bitwise_with_reference_arithmetic(kind):
-    from test_gpu_parity import run_wr
+    from support.cases import run_wr
     g = golden(f"ref90_C2_{kind}.npz")
     nt = int(g["nt"])
     hist = run_wr(kind, "C2", nt, "")
@@ -67,7 +67,7 @@ def test_time_varying_c2_bitwise_with_oracle(fp32):
     import torch
     import rwrt_oracle as O
     import synthetic as S
-    from test_gpu_time_varying import tv
+    from support.cases import tv
     eng, ob, ob0 = tv(fp32)
     cfg = S.config("C2")
     slon, slat = O.source_matrix(cfg.SW_lon, cfg.SW_lat, cfg.dlon, cfg.dlat, cfg.nnx, cfg.nny)
@@ -116,7 +116,8 @@ def held_engine(kind, lanes):
 @pytest.mark.parametrize("lanes,team", TV_HELD, ids=["pair32", "lanes64", "latency_waves"])
 @pytest.mark.parametrize("kind", KINDS)
 def test_time_varying_kernels_held_state_equal_reference(kind, lanes, team):
-    from test_gpu_parity import bitwise, run_c2
+    from support.bits import bitwise
+    from support.cases import run_c2
     eng = held_engine(kind, lanes)
     kw = dict(order_policy="cell", first_chunk=[6], team=team) if team else {}
     # the reference's own rows at 2 h, 1 d, 10 d and accepted steps (golden)

@@ -35,7 +35,7 @@ import torch
 import _hip as H
 import synthetic as S
 from shsf import SHSF, SHFilter, reference_coefficients, reference_filter
-from test_shsf_host import case_fields, definition_tolerance, harmonic_field
+from support.cases_shsf import case_fields, definition_tolerance, harmonic_field
 
 pytestmark = pytest.mark.gpu
 

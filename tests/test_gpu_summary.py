@@ -7,19 +7,18 @@ a time-varying background, through ``WR.ray_summary`` on the reference's C1
 history, across shards and ranks, and next to a density map in one ``Tee``."""
 import math
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import golden
 from density import DensityMap, DensitySink, DensitySpec, reference_bins
-from engine import Slots, Tails
 from summary import RaySummary, SummarySink, Tee, reference_summary
-from test_gpu_density import c1_wr, c2_wr, tv_engine
-from test_gpu_parity import engine, run_c2
-from test_summary_host import C1_BOX, REGIONS8, assert_summary, c1_rows, same_bits
+from support.bits import bitwise
+from support.cases import c1_wr, c2_hist, c2_wr, c2_y0, engine, tv_engine
+from support.cases_summary import C1_BOX, REGIONS8, assert_summary, c1_rows
+from support.dist import child_paths, free_port, one_rank
+from support.rows import layout_device
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -43,7 +42,7 @@ def check(rs, want, what, cols=None):
 def _same(a, b):
     """Every field of two ``numpy()`` dicts, bit for bit."""
     for k in a:
-        same = same_bits(a[k], b[k]) if a[k].dtype.kind == "f" else np.array_equal(a[k], b[k])
+        same = bitwise(a[k], b[k]) if a[k].dtype.kind == "f" else np.array_equal(a[k], b[k])
         assert same, k
 
 
@@ -93,28 +92,14 @@ def layouts(rows, frz, i0, i1, seed=1, frm=None):
     """``name -> (view, tails, slots)`` device objects of the logical rows
     ``[i0, i1)``; what a launch would not write holds SENTINEL.  ``frm``: the
     ``tail_from`` handed over (default: ``frz`` clipped to the launch)."""
-    rng = np.random.default_rng(seed + i0)
-    out = {"dense": (torch.as_tensor(rows[:, i0:i1], device=DEV).contiguous(), None, None)}
     tf = np.clip(frz, i0, i1).astype(np.int32)
-    buf = rows[:, i0:i1].copy()
-    for j in range(NRAY):
-        buf[j, tf[j] - i0:] = 0.0
-        for c, v in zip((0, 1, 3, 4), SENTINEL):
-            buf[j, tf[j] - i0:, c] = v
-    t = Tails(NRAY, DEV)
-    t.frm.copy_(torch.as_tensor(tf if frm is None else np.asarray(frm, np.int32)))
     tail = rows[np.arange(NRAY), np.minimum(tf, i1 - 1)].copy()
     tail[tf >= i1] = [SENTINEL[0], SENTINEL[1], 0.0, SENTINEL[2], SENTINEL[3], 0.0, 0.0, 0.0]   # (no tail: unread)
-    t.row.copy_(torch.as_tensor(tail))
-    out["tails"] = (torch.as_tensor(buf, device=DEV).contiguous(), t, None)
-    live = np.where(tf > i0)[0]
-    slot = np.full(NRAY, -1, np.int32)
-    slot[live] = rng.permutation(len(live)).astype(np.int32)
-    blocks = np.empty((len(live), i1 - i0, 8))
-    blocks[slot[live]] = buf[live]
-    s = Slots(NRAY, DEV)
-    s.slot.copy_(torch.as_tensor(slot))
-    out["slots"] = (torch.as_tensor(blocks, device=DEV).contiguous(), t, s)
+    L = dict(i0=i0, i1=i1, rows=rows[:, i0:i1], tail=tail, tf=tf)
+    # (here a ray has a row block when it has rows to read, whatever its number)
+    out = layout_device(L, dict(zip((0, 1, 3, 4), SENTINEL)), seed + i0, DEV, live=np.where(tf > i0)[0])
+    if frm is not None:
+        out["tails"][1].frm.copy_(torch.as_tensor(np.asarray(frm, np.int32)))
     return out
 
 
@@ -188,31 +173,6 @@ def test_identity_columns_and_argument_checks():
 
 # ------------------------------------------------ C2 through the engine
 C2_REGIONS = [C1_BOX, (160.0, 220.0, 20.0, 60.0), (150.0, 160.0, 30.0, 50.0)]   # chosen from a 10-day CPU history
-_C2 = {}
-
-
-def c2_y0(kind):
-    g = golden(f"init_C2_{kind}.npz")
-    return g["rows"].reshape(7, -1), torch.as_tensor(g["rows"][:5].reshape(5, -1))
-
-
-def c2_hist(kind, method="rk45"):
-    """The logical history ``[3072, 121, 8]`` of the 10-day C2 run as a plain
-    sink receives it (dense rows), computed once."""
-    if (kind, method) not in _C2:
-        if method == "rk45":
-            hist, _ = run_c2(kind, NT_C2)
-        else:
-            row0, y0 = c2_y0(kind)
-            got = {}
-            engine(kind).integrate_rk4(y0, NT_C2, 7200.0,
-                                       sink=lambda a, b, o: got.__setitem__(a, o.cpu().numpy().copy()))
-            hist = np.full((3072, NT_C2, 8), NAN)
-            hist[:, 0, :7] = row0.T
-            hist[:, 1:] = np.concatenate([got[k] for k in sorted(got)], axis=1)
-        hist.setflags(write=False)
-        _C2[(kind, method)] = hist
-    return _C2[(kind, method)]
 
 
 def c2_summary(kind, regions, rk4=False, idx=None, rs=None, extra=None, **kw):
@@ -370,48 +330,22 @@ def test_tee_density_and_summary_share_one_integration():
 
 
 # ------------------------------------------------------------- allreduce
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _paths():
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    sys.path[:0] = [os.path.join(root, "rossby-wave-ray-tracing_amd"), root, here]
-
-
-def _one_rank_worker(port, q):
-    _paths()
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1)
-    try:
-        import shard
-        rows, frz = crafted()
-        rs = RaySummary(NRAY, REGIONS8, "cuda:0")
-        rs.start(rows[:, 0, 0], rows[:, 0, 1], rows[:, 0, 3], rows[:, 0, 4])
-        half = torch.arange(0, NRAY, 2, device="cuda:0")          # the rays this rank integrated
-        view = torch.as_tensor(rows[::2, 1:], device="cuda:0").contiguous()
-        rs.add_rows(1, 8, view, ray=half)
-        before = rs.numpy()
-        rs.allreduce(dist.group.WORLD)
-        after = rs.numpy()
-        with np.errstate(all="ignore"):
-            alone = c2_wr().ray_summary(regions=C2_REGIONS).numpy()
-            shard.COLLECTIVE_MIN_WORLD = 1
-            grouped = c2_wr().ray_summary(regions=C2_REGIONS, group=dist.group.WORLD).numpy()
-        q.put(("ok", dist.get_backend(), before, after, alone, grouped))
-    except Exception as e:  # pragma: no cover
-        q.put(("err", repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _one_rank_body(dist, ops):
+    import shard
+    rows, frz = crafted()
+    rs = RaySummary(NRAY, REGIONS8, "cuda:0")
+    rs.start(rows[:, 0, 0], rows[:, 0, 1], rows[:, 0, 3], rows[:, 0, 4])
+    half = torch.arange(0, NRAY, 2, device="cuda:0")          # the rays this rank integrated
+    view = torch.as_tensor(rows[::2, 1:], device="cuda:0").contiguous()
+    rs.add_rows(1, 8, view, ray=half)
+    before = rs.numpy()
+    rs.allreduce(dist.group.WORLD)
+    after = rs.numpy()
+    with np.errstate(all="ignore"):
+        alone = c2_wr().ray_summary(regions=C2_REGIONS).numpy()
+        shard.COLLECTIVE_MIN_WORLD = 1
+        grouped = c2_wr().ray_summary(regions=C2_REGIONS, group=dist.group.WORLD).numpy()
+    return dist.get_backend(), before, after, alone, grouped
 
 
 def test_allreduce_one_rank_group_leaves_the_summary_unchanged():
@@ -419,15 +353,7 @@ def test_allreduce_one_rank_group_leaves_the_summary_unchanged():
     bit -- the rays this rank integrated and the ones nobody did, which keep
     their row 0 -- and WR.ray_summary with the group, through the N-rank
     branches (shard.COLLECTIVE_MIN_WORLD = 1), equals the run without one."""
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_one_rank_worker, args=(_free_port(), q))
-    p.start()
-    res = q.get(timeout=120)
-    p.join(timeout=60)
-    assert res[0] == "ok", res
-    _, backend, before, after, alone, grouped = res
+    backend, before, after, alone, grouped = one_rank(_one_rank_body)
     assert backend == "nccl"
     assert before["n_valid"][::2].max() == NROW and before["n_valid"][1::2].max() == 1
     _same(before, after)
@@ -436,7 +362,7 @@ def test_allreduce_one_rank_group_leaves_the_summary_unchanged():
 
 
 def _two_rank_worker(rank, port, q):
-    _paths()
+    child_paths()
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=2)
@@ -459,7 +385,7 @@ def test_world2_ray_summary_equals_single_gpu():
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_two_rank_worker, args=(r, port, q)) for r in range(2)]
     for p in procs:
         p.start()

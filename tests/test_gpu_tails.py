@@ -23,7 +23,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import golden
+from support.cases import c3_sample_y0
 
 pytestmark = pytest.mark.gpu
 SENTINEL = 7.25
@@ -85,16 +85,6 @@ def compare(out):
     assert rd.break_row == rt.break_row
     assert np.array_equal(bits(rd.state["state"]), bits(rt.state["state"]))
     return n_start, n_mid
-
-
-def c3_sample_y0(eng, n_dead=2048):
-    from bench import c3_sources
-    src, zcs = c3_sources(eng)
-    y0 = torch.cat([eng.initial_rows_dev(src, zc)[0][:5].reshape(5, -1) for zc in zcs], dim=1)
-    g = golden("c3_sample.npz")
-    dead = torch.nonzero(torch.isnan(y0.sum(0))).squeeze(1)[:: 397][:n_dead]
-    sel = torch.cat([torch.as_tensor(g["idx"], device=eng.device), dead])
-    return y0[:, sel].contiguous()
 
 
 @pytest.mark.parametrize("team", [0, [64, 64, 64]])

@@ -21,11 +21,12 @@ import torch
 import rwrt_oracle as O
 import synthetic as S
 from conftest import GOLDEN
+from support.bits import equal_nan, ulps
+from support.cases import DT, tv
 
 pytestmark = [pytest.mark.gpu, pytest.mark.refhost]
 
 HOT = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11]
-DT = 6 * 3600.0
 
 
 def host_fields(b):
@@ -34,10 +35,6 @@ def host_fields(b):
     bs.load_arrays(**b)
     bs.ready(xcyclic=True)
     return bs.fields
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
 
 
 @pytest.mark.parametrize("case", ["zonal", "nonzonal", "c5_1deg", "c5_025deg"])
@@ -53,37 +50,10 @@ def test_bs_ready_gpu_bitwise(case):
         lv.set_level(0, b["u"], b["v"])
         dev = lv.packed[0].cpu().numpy()
         want = ref.astype(np.float32) if fp32 else ref
-        assert same_bits(dev[..., :11], want), (case, fp32)
+        assert equal_nan(dev[..., :11], want), (case, fp32)
         assert not dev[..., 11].any()
         if fp32:
-            assert same_bits(lv.level0_f64.cpu().numpy()[..., :11], ref)
-
-
-_TV = {}
-
-
-def tv(fp32, nlev=5):
-    key = (fp32, nlev)
-    if key not in _TV:
-        from engine import RayEngine
-        from levels import Levels
-        bl = [S.background_level(j) for j in range(nlev)]
-        lv = Levels(bl[0]["lat"], bl[0]["lon"], nlev, t0=0.0, dt=DT, fp32=fp32)
-        for j, b in enumerate(bl):
-            lv.set_level(j, b["u"], b["v"])
-        ob = O.TimeVaryingBackground([O.Background(**b) for b in bl], 0.0, DT, fp32=fp32)
-        _TV[key] = (RayEngine.from_levels(lv), ob, O.Background(**bl[0]))
-    return _TV[key]
-
-
-def ulps(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    assert np.array_equal(np.isnan(a), np.isnan(b))
-    a, b = np.nan_to_num(a), np.nan_to_num(b)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        d = np.abs(a - b) / np.spacing(np.maximum(np.abs(a), np.abs(b)))
-    d[a == b] = 0
-    return d
+            assert equal_nan(lv.level0_f64.cpu().numpy()[..., :11], ref)
 
 
 @pytest.mark.parametrize("fp32", [False, True])

@@ -8,8 +8,6 @@ next to a ``DensitySink`` in one ``Tee``, across shards, through
 ``WR.ray_track`` on the reference's C1 history, and on a time-varying
 background."""
 import math
-import os
-import socket
 
 import numpy as np
 import pytest
@@ -17,39 +15,17 @@ import torch
 
 import synthetic as S
 import track as T
-from conftest import golden
 from density import DensityMap, DensitySink, DensitySpec, reference_bins
-from engine import Slots, Tails
+from engine import Tails
 from summary import Tee
-from test_gpu_density import NT_C2, c1_wr, c2_chan, c2_wr, tv_engine
-from test_gpu_parity import engine
-from test_gpu_summary import c2_hist, c2_y0
-from test_track_host import (C1_TRACK, VARIANTS, assert_track, c1_rows, crafted_history, sum_bound)
+from support.cases import NT_C2, c1_wr, c2_chan, c2_hist, c2_wr, c2_y0, engine, tv_engine
+from support.cases_track import (C1_TRACK, VARIANTS, assert_track, c1_rows, crafted_history, device_layouts,
+                                 reference_and_abs, start, sum_bound)
+from support.dist import one_rank
 from track import TrackMap, TrackSink, TrackSpec, reference_track
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-SENTINEL = (1.0, 0.1)     # lon lat of a row that must never be read: valid, in the map, deposited if it were
-
-
-def reference_and_abs(rows, chan, spec):
-    """``reference_track`` and the per-cell sums of |w| and |w vm| (the
-    sum|v| of the rounding bound) in one pass over the deposits."""
-    cnt = np.zeros(spec.shape, np.int64)
-    sums = np.zeros((2,) + spec.shape)
-    a = np.zeros((2,) + spec.shape)
-    dropped = 0
-    for d in T.deposits(rows, chan, spec):
-        if d is None:
-            dropped += 1
-            continue
-        c, iy, ix, w, wv = d
-        cnt[c, iy, ix] += 1
-        sums[0, c, iy, ix] += w
-        sums[1, c, iy, ix] += wv
-        a[0, c, iy, ix] += abs(w)
-        a[1, c, iy, ix] += abs(wv)
-    return {"cnt": cnt, "time": sums[0], "wsum": sums[1] if spec.wcol >= 0 else None, "dropped": dropped}, a
 
 
 def scaled(m, factor):
@@ -57,38 +33,6 @@ def scaled(m, factor):
 
 
 # ------------------------------------------------- crafted rows, entry point
-def device_layouts(h, i0, i1, seed=1):
-    """``name -> (view, tails, slots)`` device objects of rows [i0, i1) of the history."""
-    rows, tail, tf = h["rows"][:, i0:i1], h["tail"], h["tf"]
-    nray, nrow = rows.shape[:2]
-    out = {"dense": (torch.as_tensor(rows, device=DEV).contiguous(), None, None)}
-    buf = rows.copy()
-    cut = np.clip(tf, i0, i1)
-    for j in range(nray):
-        buf[j, cut[j] - i0:] = 0.0
-        buf[j, cut[j] - i0:, 0], buf[j, cut[j] - i0:, 1] = SENTINEL
-    t = Tails(nray, DEV)
-    t.frm.copy_(torch.as_tensor(tf))
-    t.row.copy_(torch.as_tensor(tail))
-    out["tails"] = (torch.as_tensor(buf, device=DEV).contiguous(), t, None)
-    live = np.where(np.arange(nray) % 3 != 0)[0]
-    slot = np.full(nray, -1, np.int32)
-    slot[live] = np.random.default_rng(seed).permutation(len(live)).astype(np.int32)
-    blocks = np.empty((len(live), nrow, 8))
-    blocks[slot[live]] = buf[live]
-    s = Slots(nray, DEV)
-    s.slot.copy_(torch.as_tensor(slot))
-    out["slots"] = (torch.as_tensor(blocks, device=DEV).contiguous(), t, s)
-    return out
-
-
-def start(m, rows0):
-    """Row 0 of a history ``[nray, 8]`` into the map."""
-    s = m.spec
-    return m.start(rows0[:, 0], rows0[:, 1], None if s.ncol < 0 else rows0[:, s.ncol],
-                   None if s.wcol < 0 else rows0[:, s.wcol])
-
-
 @pytest.mark.parametrize("nray", [41, 130], ids=["41-rays", "130-rays"])
 @pytest.mark.parametrize("shape", [(7, 5, 3), (64, 32, 1)], ids=["7x5x3", "64x32x1"])
 @pytest.mark.parametrize("name", sorted(VARIANTS))
@@ -391,66 +335,36 @@ def test_time_varying_background():
 
 
 # ------------------------------------------------------------- allreduce
-def _allreduce_worker(port, q):
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    sys.path[:0] = [os.path.join(root, "rossby-wave-ray-tracing_amd"), root, here]
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1)
-    try:
-        ops = []
-        f = dist.all_reduce
-        dist.all_reduce = lambda *a, **k: (ops.append(k.get("op")), f(*a, **k))[1]
-        from track import TrackMap, TrackSpec
-        rng = np.random.default_rng(0)
-        n = 2000
-        spec = TrackSpec(144, 72, weight="ug")
-        rows = np.zeros((n, 2, 8))
-        rows[..., 0] = rng.uniform(0, 6.28, (n, 1)) + rng.uniform(-0.3, 0.3, (n, 2))
-        rows[..., 1] = rng.uniform(-1.4, 1.4, (n, 1)) + rng.uniform(-0.1, 0.1, (n, 2))
-        rows[..., 4], rows[..., 5] = 1.0, rng.uniform(-2, 2, (n, 2))
-        rows[0, 1, 0] = 1e300
-        m = TrackMap(spec, n, "cuda:0")
-        m.start(rows[:, 0, 0], rows[:, 0, 1], rows[:, 0, 4], rows[:, 0, 5])
-        m.add_rows(1, 2, torch.as_tensor(rows[:, 1:], device="cuda:0"))
-        before, prev = m.numpy(), m.prev.clone()
-        m.allreduce(dist.group.WORLD)
-        after = m.numpy()
-        same_prev = bool(torch.equal(prev, m.prev))
-        nops = len(ops)
-        all_sum = all(o == dist.ReduceOp.SUM for o in ops)
-        # WR.ray_track with a group, through the N-rank branches on one rank
-        # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does)
-        import shard
-        with np.errstate(all="ignore"):
-            alone = c2_wr().ray_track(spec, by="zwn").numpy()
-            shard.COLLECTIVE_MIN_WORLD = 1
-            grouped = c2_wr().ray_track(spec, by="zwn", group=dist.group.WORLD).numpy()
-        q.put(("ok", dist.get_backend(), nops, all_sum, same_prev, before, after, alone, grouped, len(ops) - nops))
-    except Exception as e:  # pragma: no cover
-        q.put(("err", repr(e)))
-        raise
-    finally:
-        dist.destroy_process_group()
+def _allreduce_body(dist, ops):
+    rng = np.random.default_rng(0)
+    n = 2000
+    spec = TrackSpec(144, 72, weight="ug")
+    rows = np.zeros((n, 2, 8))
+    rows[..., 0] = rng.uniform(0, 6.28, (n, 1)) + rng.uniform(-0.3, 0.3, (n, 2))
+    rows[..., 1] = rng.uniform(-1.4, 1.4, (n, 1)) + rng.uniform(-0.1, 0.1, (n, 2))
+    rows[..., 4], rows[..., 5] = 1.0, rng.uniform(-2, 2, (n, 2))
+    rows[0, 1, 0] = 1e300
+    m = TrackMap(spec, n, "cuda:0")
+    m.start(rows[:, 0, 0], rows[:, 0, 1], rows[:, 0, 4], rows[:, 0, 5])
+    m.add_rows(1, 2, torch.as_tensor(rows[:, 1:], device="cuda:0"))
+    before, prev = m.numpy(), m.prev.clone()
+    m.allreduce(dist.group.WORLD)
+    after = m.numpy()
+    same_prev = bool(torch.equal(prev, m.prev))
+    nops = len(ops)
+    all_sum = all(o == dist.ReduceOp.SUM for o in ops)
+    # WR.ray_track with a group, through the N-rank branches on one rank
+    # (shard.COLLECTIVE_MIN_WORLD = 1, as tests/test_gpu_multirank.py does)
+    import shard
+    with np.errstate(all="ignore"):
+        alone = c2_wr().ray_track(spec, by="zwn").numpy()
+        shard.COLLECTIVE_MIN_WORLD = 1
+        grouped = c2_wr().ray_track(spec, by="zwn", group=dist.group.WORLD).numpy()
+    return dist.get_backend(), nops, all_sum, same_prev, before, after, alone, grouped, len(ops) - nops
 
 
 def test_allreduce_one_rank_group_leaves_the_map_unchanged():
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_allreduce_worker, args=(port, q))
-    p.start()
-    res = q.get(timeout=120)
-    p.join(timeout=60)
-    assert res[0] == "ok", res
-    _, backend, nops, all_sum, same_prev, before, after, alone, grouped, nops_wr = res
+    backend, nops, all_sum, same_prev, before, after, alone, grouped, nops_wr = one_rank(_allreduce_body)
     assert backend == "nccl" and nops == 4 and all_sum and same_prev          # cnt, time, wsum, dropped
     assert before["cnt"].sum() > 2000 and before["dropped"] == 1
     assert_track(after, before, None, "one rank")

@@ -11,8 +11,9 @@ import torch
 
 import synthetic as S
 from constants import deg2rad
-from test_gpu_parity import engine
-from test_wn_host import ZWN, bs_of, check_filled_planes, fill_planes, reference_map, same_bits
+from support.bits import equal_nan as same_bits
+from support.cases import engine
+from support.cases_wn import ZWN, bs_of, check_filled_planes, fill_planes, reference_map
 from wn import WN, reference_fill, reference_wn_map
 
 pytestmark = pytest.mark.gpu

@@ -2,10 +2,6 @@
 layouts in a stand-alone program under the sanitizers, and launch_rows.py --
 the sinks' call forms, shard cache and ``take`` against a recording fake, and
 the dispatcher ``deliver``."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 import torch
@@ -17,6 +13,7 @@ from density import DensitySink
 from engine import deliver
 from flux import FluxSink
 from summary import SummarySink
+from support import hostprog
 from track import TrackSink
 
 # the six sinks: a channel per ray (None stays None), or a column per ray (None: idx itself)
@@ -24,30 +21,12 @@ CHANNEL_SINKS = {"density": DensitySink, "arrival": ArrivalSink, "flux": FluxSin
 COLUMN_SINKS = {"summary": SummarySink, "track": TrackSink, "cross": CrossSink}
 SINKS = {**CHANNEL_SINKS, **COLUMN_SINKS}
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NRAY, I0, I1, NOUT = 16, 3, 10, 8          # 7 rows: one batch of 4 and a remainder of 3
 NROWS = I1 - I0
 # below, at and above the launch; rows read: 0 0 1 3 4 5 7 7 | 7 7 5 4 1 0 0 3
 TAIL_FROM = np.array([1, 3, 4, 6, 7, 8, 10, 12, 12, 10, 8, 7, 4, 3, 1, 6], np.int32)
 NO_BLOCK = (3, 4, 7, 10, 13)               # a third of the rays; 3, 4 and 10 with tail_from inside the launch
 GARBAGE = -777.0                           # buffer rows a ray's tail replaces: never to be read
-
-
-def _build_host_program(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "launch_rows_main")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-           "-fsanitize=undefined,address", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
-           "-o", exe, os.path.join(ROOT, "tests", "host", "launch_rows_main.cpp")]
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    if b.returncode != 0 and "sanitize" in b.stderr and "launch_rows" not in b.stderr:
-        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
 
 
 def layouts():
@@ -85,23 +64,18 @@ def test_walk_host_program_under_sanitizers(tmp_path, name):
     program built with ASan + UBSan + float-cast-overflow and run directly:
     every ray's rows come in order -- the rows read, then one tail of the right
     length -- and equal the logical rows built here."""
-    exe = _build_host_program(tmp_path)
+    exe = hostprog.build("launch_rows", tmp_path)
     logical, tf, lines = layouts()[name]
     nread = tf - I0
     assert name == "dense" or sorted(set(nread.tolist())) == [0, 1, 3, 4, 5, 7]
-    # (verify_asan_link_order=0: the environment may preload a library of its own)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    out = hostprog.run(exe, lines)
     want = []
     for j in range(NRAY):
         want += [("R", j, i, logical[j, i - I0, 0], logical[j, i - I0, 7]) for i in range(I0, int(tf[j]))]
         if tf[j] < I1:
             want.append(("T", j, int(tf[j]), I1 - int(tf[j]), logical[j, -1, 0], logical[j, -1, 7]))
     got = [(w[0],) + tuple(int(x) for x in w[1:-2]) + (float(w[-2]), float(w[-1]))
-           for w in (ln.split() for ln in r.stdout.splitlines())]
+           for w in (ln.split() for ln in out)]
     assert got == want
     # the same as rows: the walk reproduces the logical rows, and nothing else
     rows = np.full((NRAY, NROWS, 2), np.nan)

@@ -17,19 +17,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from support.cases_npmath import svml_host, trig_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "oracle", "_devmath", "libnpmath.so")
 
 
-def _svml_host():
-    try:
-        from numpy._core._multiarray_umath import __cpu_features__ as cf
-    except ImportError:
-        return False
-    return bool(cf.get("AVX512_SKX"))
-
-
-pytestmark = pytest.mark.skipif(not _svml_host(),
+pytestmark = pytest.mark.skipif(not svml_host(),
                                 reason="this host's NumPy does not dispatch SVML (no AVX512_SKX): "
                                        "its tan/power are not the reference's")
 
@@ -70,21 +64,6 @@ def assert_bitwise(got, want, x, what):
     bad = np.nonzero(g != w)[0]
     assert bad.size == 0, (f"{what}: {bad.size} of {got.size} differ, e.g. x={x[bad[0]]!r}: "
                            f"{got[bad[0]]!r} vs NumPy {want[bad[0]]!r}")
-
-
-def trig_args(rng, n):
-    half_pi = np.pi / 2
-    k = np.arange(-500, 501, dtype=np.float64)
-    edges = np.concatenate([k / 128.0, k * np.pi / 16.0, [0.126, 0.855469, 2.426265, half_pi, np.pi]])
-    edges = np.concatenate([edges, -edges])
-    near = np.concatenate([np.nextafter(edges, np.inf), np.nextafter(edges, -np.inf), edges])
-    return np.concatenate([
-        rng.uniform(-half_pi, half_pi, n),                        # latitudes
-        rng.uniform(-0.2, 0.2, n // 4),                           # half position steps
-        rng.standard_normal(n // 4) * 10.0 ** rng.uniform(-30, 0, n // 4),
-        rng.uniform(-200.0, 200.0, n // 4),                       # unwrapped longitudes
-        rng.uniform(-6.5e4, 6.5e4, n // 8),
-        near, [0.0, -0.0, 5e-324, -5e-324, 2.2250738585072014e-308, 1e-300, np.nan, np.inf, -np.inf]])
 
 
 @pytest.mark.parametrize("fn", ["sin", "cos", "tan"])

@@ -3,21 +3,14 @@ behind every ``DeviceMap.allreduce``) on the CPU: world size 2 over gloo
 (127.0.0.1), plain tensors -- the map classes themselves need a GPU
 (tests/test_gpu_multirank.py)."""
 import os
-import socket
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from support.dist import free_port
+
 INT32_MAX = 2 ** 31 - 1
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _tensors(rank):
@@ -54,7 +47,7 @@ def _worker(rank, world, port, q):
 def test_world2_gloo_min_max_sum_and_none():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -19,9 +19,9 @@ from make_devmath import TSTEP, row_hashes  # noqa: E402
 
 import rwrt_oracle as O  # noqa: E402
 import synthetic as S    # noqa: E402
-from test_np_math import _svml_host  # noqa: E402
+from support.cases_npmath import svml_host  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not _svml_host(), reason="NumPy without SVML: not the reference's arithmetic")
+pytestmark = pytest.mark.skipif(not svml_host(), reason="NumPy without SVML: not the reference's arithmetic")
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -6,7 +6,6 @@ per-rank work, global reductions, gather) can be checked against the
 unsharded result exactly.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -14,13 +13,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from support.dist import free_port
 
 
 def fake_integrate(y0):
@@ -77,7 +70,7 @@ def test_shard_indices_partition_and_balance():
 def test_world2_gloo_pipeline_equals_unsharded():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -100,7 +93,7 @@ def test_world1_collective_knob(min_world, ncoll):
     RCCL this way on the one-GPU box)."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    p = ctx.Process(target=_worker, args=(0, 1, _free_port(), q, min_world))
+    p = ctx.Process(target=_worker, args=(0, 1, free_port(), q, min_world))
     p.start()
     res = q.get(timeout=120)
     p.join(timeout=60)
@@ -181,7 +174,7 @@ def _delta_worker(rank, world, port, q):
 def test_world2_gloo_changed_rows_gather():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_delta_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -7,33 +7,19 @@ tail's closed form against row by row), and the argument checks of
 import ctypes
 import math
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import _hip as H
-from conftest import golden
 from summary import R_EARTH, Tee, reference_summary, regions_rad
+from support import hostprog
+from support.bits import bitwise
+from support.cases_summary import C1_BOX, FLOAT_FIELDS, REGIONS8, assert_summary, c1_rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TWO_PI = 2 * math.pi
 INF, NAN = math.inf, math.nan
-C1_BOX = (350.0, 20.0, 20.0, 60.0)       # across 0 degrees
-REGIONS8 = [C1_BOX, (0.0, 360.0, -90.0, 90.0), (30.0, 120.0, -20.0, 40.0), (200.0, 100.0, -90.0, 0.0),
-            (0.0, 180.0, 0.0, 90.0), (180.0, 360.0, 0.0, 90.0), (90.0, 90.0, -45.0, 45.0), (10.0, 11.0, 5.0, 6.0)]
-FLOAT_FIELDS = ("lon_first", "lat_first", "lon_last", "lat_last", "l_last", "lat_min", "lat_max", "amp_max")
-INT_FIELDS = ("n_valid", "last_row", "n_turn", "first_row", "rows_inside")
-PATH_RTOL = 1e-12
-
-
-def c1_rows():
-    """The reference's C1 history as logical rows ``[3, 1081, 8]``."""
-    hist = golden("traj_C1.npz")["hist"]              # (7, 1081, 3)
-    rows = np.full((3, hist.shape[1], 8), NAN)
-    rows[:, :, :7] = hist.transpose(2, 1, 0)
-    return rows
 
 
 def random_rows(nray=40, nt=23, seed=0):
@@ -115,25 +101,6 @@ def scalar_summary(rows, regions):
     return out
 
 
-def same_bits(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))))
-
-
-def assert_summary(got, want, what=""):
-    """Integer fields equal, selections bitwise, ``path`` within 1e-12 of
-    ``want`` (and exactly 0 where ``want`` is 0)."""
-    for k in INT_FIELDS:
-        assert got[k].dtype.kind == "i" and np.array_equal(got[k], want[k]), (what, k, got[k], want[k])
-    for k in FLOAT_FIELDS:
-        assert same_bits(got[k], want[k]), (what, k)
-    gp, wp = np.asarray(got["path"]), np.asarray(want["path"])
-    assert gp.shape == wp.shape and np.isfinite(wp).all(), what
-    err = np.abs(gp - wp)
-    assert np.all(err <= PATH_RTOL * wp), (what, float(np.max(err / np.where(wp > 0, wp, 1.0))))
-    assert np.all(gp[wp == 0.0] == 0.0), what
-
-
 @pytest.mark.parametrize("nreg", [0, 1, 8])
 def test_reference_summary_against_the_scalar_definition(nreg):
     rows = random_rows(seed=nreg)
@@ -195,23 +162,6 @@ def test_reference_summary_c1_history():
 
 
 # ------------------------------------------------ csrc/summary_rows.h on the host
-def _build_host_program(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "summary_rows_main")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-           "-fsanitize=undefined,address", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
-           "-o", exe, os.path.join(ROOT, "tests", "host", "summary_rows_main.cpp")]
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    if b.returncode != 0 and "sanitize" in b.stderr and "summary_rows" not in b.stderr:
-        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
-
-
 def chunk_bounds(nt, nchunk):
     """``nchunk`` chunks of ``[0, nt)``; the first is row 0 alone when there is more than one."""
     if nchunk == 1:
@@ -240,13 +190,7 @@ def run_host_program(exe, rows, regions, nchunk, tails=True):
     for j in range(nray):
         lines.append(" ".join(str(int(v)) for v in tfs[j]))
         lines += [" ".join(float(rows[j, i, c]).hex() for c in (0, 1, 3, 4)) for i in range(nt)]
-    # (verify_asan_link_order=0: the environment may preload a library of its own)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
-    out = [ln.split() for ln in r.stdout.splitlines()]
+    out = [ln.split() for ln in hostprog.run(exe, lines)]
     assert len(out) == nray
     f = np.array([[int(x, 16) for x in ln[:9]] for ln in out], np.uint64).view(np.float64)
     i = np.array([[int(x) for x in ln[9:]] for ln in out], np.int32).reshape(nray, 4 + 2 * len(boxes))
@@ -263,7 +207,7 @@ def test_row_update_host_program_under_sanitizers(tmp_path):
     equal reference_summary -- integers equal, selections bitwise, path within
     1e-12 -- and chunking changes no bit, path included; the program itself
     checks the tail's closed form against the row-by-row update."""
-    exe = _build_host_program(tmp_path)
+    exe = hostprog.build("summary_rows", tmp_path)
     for name, rows, regions in (("crafted", random_rows(seed=5), REGIONS8), ("crafted-1", random_rows(seed=6), [C1_BOX]),
                                 ("crafted-0", random_rows(seed=7), []), ("c1", c1_rows(), [C1_BOX])):
         want = reference_summary(rows, regions)
@@ -276,9 +220,9 @@ def test_row_update_host_program_under_sanitizers(tmp_path):
             if name.startswith("crafted"):
                 assert (tfs[:, -1] < rows.shape[1] - 1).any()          # some tails are longer than one row
             first = first or got
-            assert same_bits(got["path"], first["path"]), (name, nchunk)
+            assert bitwise(got["path"], first["path"]), (name, nchunk)
         dense, _ = run_host_program(exe, rows, regions, 2, tails=False)
-        assert same_bits(dense["path"], first["path"]), name
+        assert bitwise(dense["path"], first["path"]), name
         if name == "c1":
             assert got["n_turn"].tolist() == [0, 155, 111] and got["path"][0] == 0.0
             assert got["first_row"].tolist() == [[-1, 97, 93]] and got["rows_inside"].tolist() == [[0, 88, 93]]

@@ -6,9 +6,6 @@ launches in all three row layouts), and the argument checks of
 ``rwrt_ray_track``."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -16,11 +13,13 @@ import pytest
 
 import _hip as H
 import track as T
-from conftest import golden
-from test_arrival_host import launch_text
+from support import hostprog
+from support.abi import refused
+from support.cases_track import (C1_TRACK, NRAY, VARIANTS, abs_sums, assert_track, c1_rows, crafted_history,
+                                 launches_of, rows_of)
+from support.rows import LAYOUTS, layout_text
 from track import TrackSpec, reference_track, segment_cells
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TWO_PI = 2 * math.pi
 INF, NAN = math.inf, math.nan
 
@@ -105,20 +104,6 @@ def test_spec():
         reference_track(np.zeros((3, 4, 8)), [0, 1], s)
 
 
-# ---------------------------------------------------- the reference's C1 history
-def c1_rows():
-    hist = golden("traj_C1.npz")["hist"]              # (7, 1081, 3): lon lat k l amp ug vg
-    rows = np.full((3, 1081, 8), NAN)
-    for c in range(7):
-        rows[:, :, c] = hist[c].T
-    return rows
-
-
-# (map) -> considered segments, dropped, cell deposits, sum of time: need = 'amp', lat -90..90, max_cells = nx + ny
-C1_TRACK = {(1440, 720): (2160, 0, 42669, 2160.0), (360, 180): (2160, 0, 12271, 2160.0),
-            (7, 5): (2160, 0, 2282, 2160.0)}
-
-
 @pytest.mark.parametrize("shape", sorted(C1_TRACK))
 def test_reference_track_c1_history(shape):
     """The reference's own 90-day C1 history: two live rays of 1080 segments
@@ -142,15 +127,6 @@ def test_reference_track_c1_history(shape):
 
 
 # ------------------------------------------------------ hand-made segments
-def rows_of(points, amp=1.0, ug=2.0):
-    """One ray through ``points`` = [(lon, lat), ...] (radians)."""
-    r = np.zeros((1, len(points), 8))
-    r[0, :, 0] = [p[0] for p in points]
-    r[0, :, 1] = [p[1] for p in points]
-    r[0, :, 4], r[0, :, 5] = amp, ug
-    return r
-
-
 def grid_to_rad(spec, X, Y):
     return X / spec.inv_dlon + spec.lon0, Y / spec.inv_dlat + spec.lat0
 
@@ -281,144 +257,8 @@ def test_conservation_on_a_whole_globe_map():
     assert len({c for c, _ in seen}) == 1 and len({n for _, n in seen}) == 3
 
 
-# ------------------------------------------------------------- crafted launches
-NRAY = 41
-VARIANTS = {
-    "wrapped": dict(),
-    "wrapped-weight": dict(weight="ug"),
-    "window": dict(lon_range=(-360.0, 720.0)),
-    "window-weight-no-need": dict(lon_range=(-360.0, 720.0), weight="vg", need=None),
-    "short-segments": dict(weight="k", max_cells=3),
-}
-
-
-def crafted_history(nt, seed, nray=NRAY, tf=None, i0=1):
-    """A logical history ``[nray, nt, 8]`` (row 0 the initial row) whose rows
-    ``[i0, nt)`` all three layouts can hold as one launch: ray j's rows from
-    ``tf[j]`` on repeat its tail row.  ``tf`` runs through values below, at,
-    inside, at the end of and above the launch; the j % 3 == 0 rays (no row
-    block in the slots layout) have at most i0.  By j % 4: rays that cross a
-    few cells per row in any direction, rays that drift slowly (several rows
-    per cell, going on into the tail), rays that jump (many segments above
-    ``max_cells``) and rays that move along grid lines and through nodes of a
-    7 x 5 map (coordinates that are multiples of half a cell).  Longitudes
-    span about three circles either side of 0, latitudes leave +-90 degrees;
-    NaN and inf holes in lon, lat, amp and ug, in rows and in tails; lon =
-    1e300 in a row and in a tail; channels -1 and 3 among 0..2."""
-    rng = np.random.default_rng(seed)
-    rows = rng.uniform(-3.0, 3.0, (nray, nt, 8))
-    kind = np.arange(nray) % 4
-    lon = rng.uniform(-15.0, 15.0, (nray, 1)) + np.cumsum(rng.uniform(-1.2, 1.2, (nray, nt)), axis=1)
-    lat = rng.uniform(-1.2, 1.2, (nray, 1)) + np.cumsum(rng.uniform(-0.5, 0.5, (nray, nt)), axis=1)
-    slow = kind == 1
-    lon[slow] = rng.uniform(-6.0, 12.0, (slow.sum(), 1)) + 0.05 * np.arange(nt)
-    lat[slow] = rng.uniform(-1.0, 1.0, (slow.sum(), 1)) - 0.01 * np.arange(nt)
-    jumpy = kind == 2
-    lon[jumpy] = rng.uniform(-20.0, 20.0, (jumpy.sum(), nt))
-    lat[jumpy] = rng.uniform(-1.8, 1.8, (jumpy.sum(), nt))
-    lines = kind == 3
-    hx, hy = TWO_PI / 7 / 2, math.pi / 5 / 2                  # half a cell of the 7 x 5 map
-    lon[lines] = hx * rng.integers(-20, 21, (lines.sum(), nt))
-    lat[lines] = -math.pi / 2 + hy * rng.integers(0, 11, (lines.sum(), nt))
-    rows[..., 0], rows[..., 1] = lon, lat
-    rows[3, nt // 2, 5] = NAN                                    # holes
-    rows[7, i0, 0] = INF
-    rows[9, nt // 2, 1] = -INF
-    rows[13, i0, 4] = NAN
-    rows[17, nt - 1, 4] = INF
-    rows[4, min(i0 + 1, nt - 1), 0] = 1e300                      # finite: dropped on both sides
-    rows[21, :, 0:2] = rows[21, :1, 0:2]                         # at rest while it is read
-    tail = rows[:, -1].copy()
-    tail[:, 0] += rng.uniform(-0.8, 0.8, nray)
-    tail[5::7, 0] = NAN
-    tail[6::11, 4] = INF
-    tail[8::13, 5] = NAN
-    tail[10, 0] = 1e300
-    if tf is None:
-        i1 = nt
-        choice = sorted({i0 - 2, i0, i0 + 1, i0 + 3, i0 + 4, i0 + 5, i1 - 1, i1, i1 + 3})
-        j = np.arange(nray)
-        q = np.cumsum(j % 3 != 0)                                 # (the rays with a block take every value)
-        tf = np.where(j % 3 == 0, np.array([i0 - 2, i0])[(j // 3) % 2], np.array(choice)[q % len(choice)])
-    tf = np.asarray(tf, np.int32)
-    cut = np.clip(tf, i0, nt)
-    for j in range(nray):
-        rows[j, cut[j]:] = tail[j]
-    # a slow ray whose tail continues its last cell: the run goes on into the tail
-    for j in np.where(slow)[0]:
-        if i0 < cut[j] < nt:
-            tail[j] = rows[j, cut[j] - 1]
-            rows[j, cut[j]:] = tail[j]
-    chan = rng.integers(-1, 4, nray).astype(np.int32)            # -1 and nchan = 3 among them
-    return dict(rows=rows, tail=tail, tf=tf, chan=chan)
-
-
-def launches_of(h, bounds, layout):
-    """The history as launches: row 0 as a dense launch [0, 1), then the
-    launches ``bounds`` = [(i0, i1), ...] in ``layout`` (the tails of a launch
-    that ends before the history's tail starts are above it)."""
-    out = [(dict(i0=0, i1=1, rows=h["rows"][:, :1], tail=h["tail"], tf=np.full(len(h["tf"]), 1), chan=h["chan"]),
-            "dense")]
-    for i0, i1 in bounds:
-        out.append((dict(i0=i0, i1=i1, rows=h["rows"][:, i0:i1], tail=h["tail"], tf=h["tf"], chan=h["chan"]), layout))
-    return out
-
-
-def abs_sums(rows, chan, spec):
-    """Per cell the sum of |w| and of |w vm| of its deposits: the sum|v| of the
-    rounding bound."""
-    a = np.zeros((2,) + spec.shape)
-    for d in T.deposits(rows, chan, spec):
-        if d is not None:
-            c, iy, ix, w, wv = d
-            a[0, c, iy, ix] += abs(w)
-            a[1, c, iy, ix] += abs(wv)
-    return a
-
-
-def sum_bound(cnt, abs_sum):
-    """|got - ref| <= 2 (n + 1) 2^-53 sum|v| per cell: the bound of a sum of n
-    terms in any order, twice (both sides are rounded sums), plus one rounding
-    for a tail added as a product (tests/test_gpu_density.py)."""
-    return 2.0 * (cnt + 1) * 2.0 ** -53 * abs_sum
-
-
-def assert_track(got, want, a=None, what=""):
-    """cnt and dropped exactly; time and wsum exactly (``a`` None) or to the bound."""
-    assert got["cnt"].dtype == np.int64 and np.array_equal(got["cnt"], want["cnt"]), (what, "cnt")
-    assert int(got["dropped"]) == int(want["dropped"]), (what, "dropped", got["dropped"], want["dropped"])
-    for q, name in enumerate(("time", "wsum")):
-        if want[name] is None:
-            assert got[name] is None, (what, name)
-            continue
-        assert np.all(np.isfinite(got[name])), (what, name)
-        if a is None:
-            assert np.array_equal(got[name], want[name]), (what, name)
-        else:
-            err = np.abs(got[name] - want[name])
-            assert np.all(err <= sum_bound(want["cnt"], a[q])), (what, name, float(err.max()))
-
-
-def _build_host_program(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "track_cells_main")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-           "-fsanitize=undefined,address", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
-           "-fno-omit-frame-pointer",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
-           "-o", exe, os.path.join(ROOT, "tests", "host", "track_cells_main.cpp")]
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    if b.returncode != 0 and "sanitize" in b.stderr and "track_cells" not in b.stderr:
-        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
-
-
-@pytest.fixture(scope="module")
-def host_program(tmp_path_factory):
-    return _build_host_program(tmp_path_factory.mktemp("track_host"))
+# ------------------------------------------- csrc/track_cells.h on the host
+host_program = hostprog.fixture("track_cells")
 
 
 def run_host_program(exe, spec, launches):
@@ -426,14 +266,8 @@ def run_host_program(exe, spec, launches):
     lines = [f"{c.nx} {c.ny} {c.nchan} {c.mode} {c.need} {c.wcol} {c.max_cells} " + " ".join(
         float(x).hex() for x in (c.lon0, c.inv_dlon, c.lat0, c.inv_dlat)), str(len(launches))]
     for L, layout in launches:
-        lines += launch_text(L, layout)
-    # (verify_asan_link_order=0: the environment may preload a library of its own)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
-    out = r.stdout.splitlines()
+        lines += layout_text(L, layout)
+    out = hostprog.run(exe, lines)
     cnt = np.array(out[0].split(), np.int64).reshape(spec.shape)
     time, wsum = (np.array([float.fromhex(x) for x in out[q].split()]).reshape(spec.shape) for q in (1, 2))
     dropped, flushes = int(out[3].split()[1]), int(out[4].split()[1])
@@ -455,7 +289,7 @@ def test_walk_host_program_under_sanitizers(host_program, name):
     assert_same(want, scalar, name)
     a = abs_sums(h["rows"], h["chan"], spec)
     assert want["cnt"].sum() > 50 and np.count_nonzero(want["cnt"]) > 15 and 0 < want["dropped"] < considered
-    for layout in ("dense", "tails", "slots"):
+    for layout in LAYOUTS:
         got, flushes = run_host_program(host_program, spec, launches_of(h, [(1, 8)], layout))
         print(f"{name} {layout}: {want['cnt'].sum()} cells, {flushes} flushes, {want['dropped']} dropped")
         assert_track(got, want, a, (name, layout))
@@ -556,9 +390,7 @@ def test_track_argument_errors_without_a_gpu():
         (dict(m=good, wsum=64), b"d_wsum"), (dict(m=m(wcol=5)), b"d_wsum"),
     ]
     for kw, word in cases:
-        assert _call(lib, **kw) == H.RWRT_ERR_ARG, kw
-        assert word in lib.rwrt_last_error(), (kw, lib.rwrt_last_error())
-        assert lib.rwrt_last_error().startswith(b"rwrt_ray_track: ")
+        refused(lib, _call, kw, word, b"rwrt_ray_track: ")
     # the output pointers are checked with no rays too
     assert _call(lib, good, nray=0, rows=None, cnt=None) == H.RWRT_ERR_ARG
     # no rays: a no-op (no device is touched; there is none on the build host)

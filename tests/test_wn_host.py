@@ -4,9 +4,6 @@ node, the fill definition ``wn.reference_fill`` against a plain scalar loop,
 the shared per-entry arithmetic csrc/wn_fill.h in a stand-alone program under
 the sanitizers, and the argument checks of ``rwrt_wn_map`` / ``rwrt_wn_fill``."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,38 +11,12 @@ import pytest
 import _hip as H
 import rwrt_oracle as O
 import synthetic as S
-from wn import reference_fill, reference_wn_map
+from support import hostprog
+from support.bits import equal_nan
+from support.cases_wn import ZWN, bs_of, check_filled_planes, fill_planes, reference_map
+from wn import reference_fill
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN, INF = np.nan, np.inf
-ZWN = (1.0, 3.0, 5.0, 7.0)
-_MAPS = {}
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
-
-
-def bs_of(kind, xcyclic=True, res=2.5):
-    from bs import BS
-    bg = S.background(kind, res=res)
-    bs = BS(len(bg["lon"]), len(bg["lat"]))
-    bs.load_arrays(**bg)
-    bs.ready(xcyclic=xcyclic)
-    return bs
-
-
-def reference_map(kind, zwn=ZWN, freq=0.0, xcyclic=True, res=2.5):
-    """``reference_wn_map`` of a synthetic background, computed once and shared
-    (read-only) by the tests of this file and of tests/test_gpu_wn.py."""
-    key = (kind, tuple(zwn), float(freq), xcyclic, res)
-    if key not in _MAPS:
-        out = reference_wn_map(bs_of(kind, xcyclic, res), zwn, freq)
-        for a in out:
-            a.setflags(write=False)
-        _MAPS[key] = out
-    return _MAPS[key]
 
 
 # ------------------------------------------------- the map against the oracle
@@ -64,7 +35,7 @@ def test_reference_map_equals_the_oracles_initial_rays():
         for j in range(1, 72):
             rows = O.ray_initial(bg, bs.lon, np.full(144, bs.lat[j]), zwn, 0.0)
             for got, v in ((mwn, 3), (ug, 5), (vg, 6)):
-                assert same_bits(got[:, j], rows[v].transpose(1, 2, 0)), (j, v)
+                assert equal_nan(got[:, j], rows[v].transpose(1, 2, 0)), (j, v)
             assert np.array_equal(rootnum[:, j], (~np.isnan(rows[3])).sum(axis=0)), j
         for j in (0, 72):
             with pytest.raises(np.linalg.LinAlgError):
@@ -93,25 +64,6 @@ def test_reference_map_k_zero():
     assert np.isnan(mwn[:, :, 0]).all() and (rootnum[:, :, 0] == 0).all()
     assert not ug[:, :, 0].any() and not vg[:, :, 0].any()
     assert (rootnum[:, [0, 72], 1] == -1).all() and (rootnum[:, 1:72, 1] >= 0).all()
-
-
-# ----------------------------------------------------------- the fill's planes
-def fill_planes():
-    """``[7, 5, 6]``: an isolated NaN; a 3 x 3 NaN block; NaNs on both longitude
-    seams and both latitude edges; an inf neighbour; an all-NaN plane; a plane
-    without NaN."""
-    a = np.random.default_rng(11).standard_normal((7, 5, 6))
-    a[3, 2, 0] = NAN
-    a[2:5, 1:4, 1] = NAN
-    for i, j in ((0, 2), (6, 2), (3, 0), (3, 4), (0, 0), (6, 4), (6, 0), (0, 3)):
-        a[i, j, 2] = NAN
-    a[3, 2, 3] = NAN
-    a[2, 2, 3] = INF
-    a[6, 1, 3] = NAN
-    a[0, 0, 3] = -INF
-    a[:, :, 4] = NAN
-    a.setflags(write=False)
-    return a
 
 
 def scalar_fill(a, cyclic):
@@ -143,60 +95,24 @@ def scalar_fill(a, cyclic):
     return out
 
 
-def check_filled_planes(a, got, cyclic):
-    """What the planes of ``fill_planes`` must show, whoever filled them."""
-    keep = ~np.isnan(a)
-    assert same_bits(got[keep], a[keep])                       # non-NaN entries are copied
-    assert not np.isnan(got[3, 2, 0])                          # the isolated NaN is filled
-    assert np.isnan(got[3, 2, 1])                              # the block's centre stays NaN
-    assert not np.isnan(np.delete(got[2:5, 1:4, 1].ravel(), 4)).any()
-    assert not np.isnan(got[:, :, 2]).any()
-    assert got[3, 2, 3] == INF                                 # an infinite neighbour counts
-    assert got[6, 1, 3] == (-INF if cyclic else got[6, 1, 3]) and not np.isnan(got[6, 1, 3])
-    assert np.isnan(got[:, :, 4]).all()
-    assert same_bits(got[:, :, 5], a[:, :, 5])
-
-
 @pytest.mark.parametrize("cyclic", [True, False])
 def test_reference_fill_against_the_scalar_definition(cyclic):
     a = fill_planes()
     got = reference_fill(a, cyclic)
-    assert same_bits(got, scalar_fill(a, cyclic))
+    assert equal_nan(got, scalar_fill(a, cyclic))
     check_filled_planes(a, got, cyclic)
     # the seam: (0, 2) of plane 2 sees column 6 only when cyclic
     other = reference_fill(a, not cyclic)
-    assert not same_bits(got[[0, 6], :, 2], other[[0, 6], :, 2])
+    assert not equal_nan(got[[0, 6], :, 2], other[[0, 6], :, 2])
     # a trailing axis of any shape is a set of planes
-    assert same_bits(reference_fill(a.reshape(7, 5, 2, 3), cyclic), got.reshape(7, 5, 2, 3))
+    assert equal_nan(reference_fill(a.reshape(7, 5, 2, 3), cyclic), got.reshape(7, 5, 2, 3))
 
 
 # ------------------------------------------------- csrc/wn_fill.h on the host
-def _build_host_program(tmp_path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = str(tmp_path / "wn_fill_main")
-    cmd = [cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
-           "-fsanitize=undefined,address", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rossby-wave-ray-tracing_amd", "csrc"),
-           "-o", exe, os.path.join(ROOT, "tests", "host", "wn_fill_main.cpp")]
-    b = subprocess.run(cmd, capture_output=True, text=True)
-    if b.returncode != 0 and "sanitize" in b.stderr and "wn_fill" not in b.stderr:
-        pytest.skip("this toolchain has no sanitizer runtime: " + b.stderr[-300:])
-    assert b.returncode == 0, b.stderr[-3000:]
-    assert "warning" not in b.stderr, b.stderr[-3000:]
-    return exe
-
-
 def run_host_program(exe, a, cyclic):
     lines = ["%d %d %d %d" % (a.shape + (int(cyclic),))]
     lines += ["%016x" % u for u in np.ascontiguousarray(a).view(np.uint64).ravel().tolist()]
-    # (verify_asan_link_order=0: the environment may preload a library of its own)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    r = hostprog.run_process(exe, lines)
     out = np.array([int(x, 16) for x in r.stdout.split()], np.uint64).view(np.float64)
     return out.reshape(a.shape)
 
@@ -205,13 +121,13 @@ def test_fill_host_program_under_sanitizers(tmp_path):
     """csrc/wn_fill.h (what the kernel calls) in a stand-alone program built
     with ASan + UBSan and run directly reproduces reference_fill exactly, on
     the crafted planes and on one-column and one-row arrays."""
-    exe = _build_host_program(tmp_path)
+    exe = hostprog.build("wn_fill", tmp_path, float_cast=False, no_warnings=True)
     a = fill_planes()
     thin = np.array([[[NAN], [1.0], [NAN], [NAN], [4.0]]])          # [1, 5, 1]
     for arr in (a, thin, np.ascontiguousarray(thin.transpose(1, 0, 2)), a[:2]):
         for cyclic in (True, False):
             got = run_host_program(exe, np.ascontiguousarray(arr), cyclic)
-            assert same_bits(got, reference_fill(arr, cyclic)), (arr.shape, cyclic)
+            assert equal_nan(got, reference_fill(arr, cyclic)), (arr.shape, cyclic)
     check_filled_planes(a, run_host_program(exe, a, True), True)
 
 
