@@ -78,9 +78,38 @@ typedef struct {
   double min_step;  /* Global_Minstep              rkf45.py:362    */
   double cut_off;   /* jump mask threshold, rad    wr.py:170       */
   int32_t nt;       /* rows of the history         wr.py:157       */
-  int32_t reserved;
+  int32_t flags;    /* RWRT_PARAMS_*; 0: the reference's forward loop */
   double tstep;     /* output interval = RK4 step  wr.py:147       */
-} rwrt_params;
+} rwrt_params;      /* 48 bytes */
+
+/* rwrt_params.flags (the former `reserved` word: same offset, same size).
+ *
+ * RWRT_PARAMS_BACKWARD: backward ray tracing -- the reference's DP5(4) loop
+ * (WR.core_ray_run_rk45 over RK45) with direction = -1 (rkf45.py:207,
+ * 426-429).  Output row i is the ray's state at time -d_tbound[i]: d_tbound
+ * stays the non-negative elapsed times, the loop steps to their negatives.
+ * Everything else is the forward loop's: the step control (h_abs, the
+ * min_step clamp -- min_step is positive --, the accept and reject factors),
+ * the pole and jump masks against the previous row, ug and vg of a row as the
+ * true group velocity there (not negated), the nacc column, frozen rays
+ * repeating their row, and the three row layouts (dense, tails, slots), the
+ * queue order, n_heavy and time chunking.  The RHS is autonomous and IEEE
+ * negation is exact, so the rows equal the forward integration of -f bit for
+ * bit.
+ * Honoured by rwrt_rk45_init (h_abs depends on the direction through
+ * select_initial_step's trial point y0 + h0 * direction * f0) and by
+ * rwrt_rk45_run, rwrt_rk45_run_tails and rwrt_rk45_run_slots; init and every
+ * run call of one integration carry the same flag.  Between calls d_state
+ * holds, besides y and h_abs, f = the RHS at y (not negated) and t = minus
+ * the elapsed time (the last row's -d_tbound; a ray frozen at a call's start
+ * gets the positive value from the fill kernels: its t is never read again).
+ * The diagnostic trace (rwrt_ctx_set_trace) is not recorded by backward calls.
+ * Every other entry with an rwrt_params argument -- rwrt_rk4_run, the _tv
+ * entries, the _stack entries -- returns RWRT_ERR_ARG before any HIP call when the flag
+ * is set, and every entry returns RWRT_ERR_ARG for any other non-zero bit;
+ * the message starts with the entry point's name.  (rwrt_kat_rk45 takes no
+ * rwrt_params: it has no way to be asked for a backward run.) */
+#define RWRT_PARAMS_BACKWARD 1
 
 /* A time-varying basic state (this framework's extension for BASELINE
  * configs[4]; the reference's fun ignores t, wr.py:784-789): nlev packed

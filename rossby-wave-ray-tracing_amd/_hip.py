@@ -51,8 +51,11 @@ class Grid(ctypes.Structure):
 class Params(ctypes.Structure):
     _fields_ = [("rtol", ctypes.c_double), ("atol", ctypes.c_double),
                 ("min_step", ctypes.c_double), ("cut_off", ctypes.c_double),
-                ("nt", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("nt", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("tstep", ctypes.c_double)]
+
+
+PARAMS_BACKWARD = 1   # RWRT_PARAMS_BACKWARD (rwrt_params.flags): the DP5(4) loop's direction is -1
 
 
 class Background(ctypes.Structure):

@@ -570,8 +570,15 @@ __device__ __forceinline__ void lookup_end(const CachedStaticBG& B, const Cached
 // DESIGN.md section 21.  When a kernel is added to this file, llvm-readelf -S
 // on the device code object shows what is left of it: .text's address modulo
 // 0x200000 was 0x13f00 without the stack kernels.
+// The three backward kernels (rk45_init_back_kernel, rk45_run_back_kernel<>)
+// added 0x1140 bytes in front of .text; their code lies behind every other
+// kernel's (they are instantiated from the last functions of this file: as
+// plain kernels beside the forward ones they moved every later kernel by
+// 0x9800 to 0x9f100 bytes).  The block shrank from 0x1FEA00 by the 0x1140
+// bytes: .text stays at 0x213f00 and every kernel of the parent at its
+// address (profiles/backward/device_asm_identity.txt).
 #ifndef RWRT_PLACEMENT_PAD
-#define RWRT_PLACEMENT_PAD 0x1FEA00
+#define RWRT_PLACEMENT_PAD 0x1FD8C0
 #endif
 __device__ __attribute__((used)) static const char kPlacementPad[RWRT_PLACEMENT_PAD] = {1};
 
@@ -2372,8 +2379,9 @@ struct IsPair : std::false_type {};
 template <>
 struct IsPair<RayProblemT<PairVaryingBG64>> : std::true_type {};
 
-// select_initial_step (rkf45.py:34-99), direction = +1
-template <class P>
+// select_initial_step (rkf45.py:34-99); kBack: direction = -1 (the trial point
+// lies at t0 - h0, y0 - h0 f0; d0, d1, d2 are even in the sign)
+template <class P, bool kBack = false>
 __device__ __forceinline__ double initial_step(const P& fun, double t0, const double* y0,
                                                const double* f0, double rtol, double atol) {
   constexpr int NV = P::NV;
@@ -2391,8 +2399,8 @@ __device__ __forceinline__ double initial_step(const P& fun, double t0, const do
   if (d0 < 1e-5) h0 = 1e-6;
   if (d1 < 1e-5) h0 = 1e-6;
 #pragma unroll
-  for (int v = 0; v < NV; ++v) y1[v] = y0[v] + h0 * f0[v];
-  fun(t0 + h0, y1, f1);
+  for (int v = 0; v < NV; ++v) y1[v] = kBack ? y0[v] - h0 * f0[v] : y0[v] + h0 * f0[v];
+  fun(kBack ? t0 - h0 : t0 + h0, y1, f1);
   double s2 = 0.0;
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
@@ -2427,8 +2435,10 @@ struct Lane {
 
   // Returns kStep (attempt made, interval not finished), kReached (t == t_bound)
   // or kFrozen (NaN mean at step start: t := t_bound, y never changes again).
+  // kBack: time runs down (direction = -1): t, tb <= 0, the step is -hs.
   enum { kStep = 0, kReached = 1, kFrozen = 2 };
 
+  template <bool kBack = false>
   __device__ __forceinline__ int iterate(const P& fun, double tb, double min_step, double rtol,
                                          double atol, int64_t& nacc, int64_t& nrej) {
     if (!in_step) {
@@ -2447,9 +2457,9 @@ struct Lane {
       rejected = false;
       in_step = true;
     }
-    double h = hs;                          // h_abs * direction
+    double h = kBack ? -hs : hs;            // h_abs * direction
     double tn = t + h;
-    if (tn - tb > 0.0) tn = tb;             // rkf45.py:429
+    if (kBack ? tn - tb < 0.0 : tn - tb > 0.0) tn = tb;   // rkf45.py:429
     h = tn - t;
     const double ha = fabs(h);
     double yn[NV], k6[NV];
@@ -2484,7 +2494,7 @@ struct Lane {
     rejected = rejected || !acc;
     nacc += acc ? 1 : 0;
     nrej += acc ? 0 : 1;
-    return (acc && t - tb >= 0.0) ? kReached : kStep;   // rkf45.py:250
+    return (acc && (kBack ? t - tb <= 0.0 : t - tb >= 0.0)) ? kReached : kStep;   // rkf45.py:250
   }
 };
 
@@ -2588,6 +2598,46 @@ __global__ void rk45_init_kernel(InitArgs<BG> a) {
       P(0.0, y, f);                                   // RungeKutta.__init__: f = fun(t, y)
       habs = initial_step(P, 0.0, y, f, a.rtol, a.atol);
     }
+#pragma unroll
+    for (int v = 0; v < 5; ++v) {
+      a.state[v * a.nray + i] = y[v];
+      a.state[(5 + v) * a.nray + i] = f[v];
+    }
+    a.state[10 * a.nray + i] = 0.0;
+    a.state[11 * a.nray + i] = habs;
+    a.count[2 * i] = 0;
+    a.count[2 * i + 1] = 0;
+    a.nanrow[i] = a.nt;
+    const double mean = ((((y[0] + y[1]) + y[2]) + y[3]) + y[4]) / 5.0;
+    const bool live = !isnan(mean);
+    a.live[i] = live ? 1 : 0;
+    if (live) {
+      atomicAdd(reinterpret_cast<unsigned long long*>(&a.summary[0]), 1ull);
+      if (!isnan(habs)) atomicAdd(reinterpret_cast<unsigned long long*>(&a.summary[1]), 1ull);
+    }
+  }
+}
+
+// RWRT_PARAMS_BACKWARD: rk45_init_kernel<StaticBG> with direction = -1 (a
+// kernel of its own: rk45_init_kernel keeps its code).  f is the RHS itself
+// (not negated) and t = 0 either way; only h_abs depends on the direction,
+// through select_initial_step's trial point.
+// (A template, like rk45_run_back_kernel, and launched only from
+// launch_init_back / launch_run_back at the end of this file: the compiler
+// then places the three backward kernels behind every other kernel of the
+// code object, and none of those moves -- "Code placement" above.)
+template <bool kBack>
+__global__ void rk45_init_back_kernel(InitArgs<StaticBG> a) {
+  static_assert(kBack, "the forward kernel is rk45_init_kernel");
+  nm_stage<NM_ALL>();
+  const RayProblemT<StaticBG> P{a.B};
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.nray;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    double y[5], f[5];
+#pragma unroll
+    for (int v = 0; v < 5; ++v) y[v] = a.y0[v * a.nray + i];
+    P(0.0, y, f);
+    const double habs = initial_step<RayProblemT<StaticBG>, kBack>(P, 0.0, y, f, a.rtol, a.atol);
 #pragma unroll
     for (int v = 0; v < 5; ++v) {
       a.state[v * a.nray + i] = y[v];
@@ -3015,7 +3065,7 @@ __device__ __forceinline__ bool quad_dis_reaches(const QuadRole& R, double lon_c
 // hand-off of rk45_run_kernel's waves, run_rays): rows [it, it_end) of `ray`,
 // its mid-step state included (in_step, rejected, hs), exactly where a run
 // kernel lane left it between two attempts
-template <bool kTrace>
+template <bool kTrace, bool kBack = false>
 __device__ __forceinline__ void quad_run(const RunArgs<StaticBG>& a, const CachedStaticBG& B, const QuadRole& R,
                                          KQuad& K, int64_t ray, double* rows, double (&y)[5], double (&f)[5],
                                          double (&aux)[3], double t, double habs, double hs, int64_t nacc,
@@ -3024,7 +3074,7 @@ __device__ __forceinline__ void quad_run(const RunArgs<StaticBG>& a, const Cache
                                          int64_t w) {
   const bool writer = R.role == 0;
   for (;;) {
-    const double tb = a.tbound[it];
+    const double tb = kBack ? -a.tbound[it] : a.tbound[it];
     // ---- Lane::iterate (rkf45.py:222-253, 375-514)
     int st = 0;   // 0 step, 1 reached, 2 frozen
     if (!in_step) {
@@ -3041,8 +3091,8 @@ __device__ __forceinline__ void quad_run(const RunArgs<StaticBG>& a, const Cache
       }
     }
     if (st == 0) {
-      double tn = t + hs;
-      if (tn - tb > 0.0) tn = tb;
+      double tn = kBack ? t - hs : t + hs;
+      if (kBack ? tn - tb < 0.0 : tn - tb > 0.0) tn = tb;
       const double h = tn - t;
       const double ha = fabs(h);
       double yn[5], k6[5];
@@ -3069,7 +3119,7 @@ __device__ __forceinline__ void quad_run(const RunArgs<StaticBG>& a, const Cache
       nacc += acc ? 1 : 0;
       nrej += acc ? 0 : 1;
       MARK("control_done");
-      if (!(acc && t - tb >= 0.0)) continue;
+      if (!(acc && (kBack ? t - tb <= 0.0 : t - tb >= 0.0))) continue;
       st = 1;
     }
     // ---- interval it reached: rk45_run_kernel's post-processing (wr.py:835-885)
@@ -3111,7 +3161,7 @@ __device__ __forceinline__ void quad_run(const RunArgs<StaticBG>& a, const Cache
     prev_lat = y[1];
     cos_prev = cos_c;
     it = last;
-    if (st == 2) t = a.tbound[a.it_end - 1];
+    if (st == 2) t = kBack ? -a.tbound[a.it_end - 1] : a.tbound[a.it_end - 1];
     if (it == a.it_end) {
       if (writer) {   // the ray's last row of the call (tails)
         if (double* const lr = last_rows(a))
@@ -3136,7 +3186,7 @@ __device__ __forceinline__ void quad_run(const RunArgs<StaticBG>& a, const Cache
   }
 }
 
-template <bool kTrace>
+template <bool kTrace, bool kBack = false>
 __device__ __forceinline__ void quad_rays(const RunArgs<StaticBG>& a, char* cache, double* Kq, int lb) {
   const CachedStaticBG B = LaneBG<StaticBG>::make(a.B, cache);
   QuadRole R;
@@ -3175,7 +3225,7 @@ __device__ __forceinline__ void quad_rays(const RunArgs<StaticBG>& a, char* cach
   double prev_lon = y[0], prev_lat = y[1], cos_prev = k_cos(prev_lat);
   aux[2] = kNaN;
   bool in_step = false, rejected = false;
-  quad_run<kTrace>(a, B, R, K, ray, rows, y, f, aux, t, habs, hs, nacc, nrej, att0, nanrow, it, prev_lon,
+  quad_run<kTrace, kBack>(a, B, R, K, ray, rows, y, f, aux, t, habs, hs, nacc, nrej, att0, nanrow, it, prev_lon,
                    prev_lat, cos_prev, in_step, rejected, w);
 }
 
@@ -3207,7 +3257,7 @@ struct TvBlock<VaryingBG<T>> {
 // work queue (hw = -1), or -- kReplica, the time-varying latency mode -- every
 // lane of the wave runs the ray at order position hw, replicated, through a
 // BlockVaryingBG, and lane 0 stores its rows and state.
-template <class BG, class LBG, bool kTrace, bool kReplica, bool kPair = false>
+template <class BG, class LBG, bool kTrace, bool kReplica, bool kPair = false, bool kBack = false>
 __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, char* smem, int64_t hw) {
   using RayProblem = RayProblemT<LBG>;
   const RayProblem P{lbg};
@@ -3283,8 +3333,8 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
         }
       }
     }
-    const double tb = a.tbound[it];
-    const int st = L.iterate(P, tb, a.min_step, a.rtol, a.atol, nacc, nrej);
+    const double tb = kBack ? -a.tbound[it] : a.tbound[it];
+    const int st = L.template iterate<kBack>(P, tb, a.min_step, a.rtol, a.atol, nacc, nrej);
     if (st == Lane<RayProblem, KStore>::kStep) continue;
     MARK("x_row_end");
 
@@ -3350,7 +3400,7 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
     prev_lat = y[1];
     cos_prev = cos_c;
     it = last;
-    if (st == Lane<RayProblem, KStore>::kFrozen) L.t = a.tbound[a.it_end - 1];
+    if (st == Lane<RayProblem, KStore>::kFrozen) L.t = kBack ? -a.tbound[a.it_end - 1] : a.tbound[a.it_end - 1];
     if (it == a.it_end && writer) {
       // its last row of the call (tails), first: r0..r3 die here
       if (double* const lr = last_rows(a)) store_tail(lr, ray, r0, r1, r2, r3);
@@ -3416,7 +3466,7 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
         R.odd = (R.role & 1) != 0;
         R.high = (R.role & 2) != 0;
         KQuad K{reinterpret_cast<double*>(smem) + threadIdx.x};
-        quad_run<false>(a, QB, R, K, qray, qrows, y, f, aux, qt, qhabs, qhs, qnacc, qnrej, 0, qnanrow, qit,
+        quad_run<false, kBack>(a, QB, R, K, qray, qrows, y, f, aux, qt, qhabs, qhs, qnacc, qnrej, 0, qnanrow, qit,
                         qplon, qplat, qcos, (qflags & 1) != 0, (qflags & 2) != 0, 0);
       }
     }
@@ -3478,6 +3528,33 @@ rk45_run_kernel(RunArgs<BG> a) {
                                                     -1);
   else
     run_rays<BG, typename LaneBG<BG>::type, kTrace, false>(a, LaneBG<BG>::make(a.B, smem + kKBytes), smem, -1);
+}
+
+// RWRT_PARAMS_BACKWARD: rk45_run_kernel<StaticBG> with direction = -1 as a
+// compile-time constant (Lane::iterate<true>, quad_run<.., true>): rows
+// [it_begin, it_end) are the states at -tbound[it], the step is -hs, the clip
+// and the arrival test are mirrored; the RHS, the step control, the masks and
+// the rows' ug, vg are the forward loop's.  Both tiers, the latency mode and
+// the drain-time hand-off as forward; no trace instantiation.
+template <bool kLean>
+__global__ void __launch_bounds__(256, 1) __attribute__((aligned(RWRT_RUN_ALIGN)))
+rk45_run_back_kernel(RunArgs<StaticBG> a) {
+  if (bg_lean(a.B.range, a.B.F) != kLean) return;   // (launch-uniform)
+  nm_stage<NM_ALL>();
+  constexpr int kKBytes = 5 * 5 * 256 * 8;
+  __shared__ __attribute__((aligned(16))) char smem[kKBytes + LaneBG<StaticBG>::kLdsBytes];
+  const int lb = (int)blockIdx.x;
+  if (RARE(lb < a.heavy_blocks)) {   // (block-uniform) latency mode
+    __builtin_amdgcn_s_setprio(1);
+    quad_rays<false, true>(a, smem + kKBytes, reinterpret_cast<double*>(smem), lb);
+    return;
+  }
+  if constexpr (kLean)
+    run_rays<StaticBG, LeanCachedStaticBG, false, false, false, true>(
+        a, LeanCachedStaticBG{LaneBG<StaticBG>::make(a.B, smem + kKBytes)}, smem, -1);
+  else
+    run_rays<StaticBG, typename LaneBG<StaticBG>::type, false, false, false, true>(
+        a, LaneBG<StaticBG>::make(a.B, smem + kKBytes), smem, -1);
 }
 
 // ---------------------------------------------------------------------------
@@ -3979,6 +4056,17 @@ rwrt_status check_launch(const char* what) {
   return RWRT_OK;
 }
 
+// rwrt_params.flags as the entry point `fn` takes them, before any HIP call:
+// no bit beyond RWRT_PARAMS_BACKWARD, and that one only where the entry has a
+// backward loop (the static DP5(4) entries).  A NULL p is the entry's own error.
+rwrt_status check_flags(const char* fn, const rwrt_params* p, bool backward_ok) {
+  if (!p || p->flags == 0) return RWRT_OK;
+  if (p->flags & ~RWRT_PARAMS_BACKWARD) return fail(RWRT_ERR_ARG, "%s: params.flags has a bit that is not defined", fn);
+  if (!backward_ok)
+    return fail(RWRT_ERR_ARG, "%s: RWRT_PARAMS_BACKWARD is taken by the static DP5(4) entries only (rwrt_rk45_init, rwrt_rk45_run*)", fn);
+  return RWRT_OK;
+}
+
 rwrt_status make_field(const rwrt_grid* g, const double* packed, Field& F) {
   if (!g) return fail(RWRT_ERR_ARG, "grid is NULL%s");
   if (!packed) return fail(RWRT_ERR_ARG, "packed fields pointer is NULL%s");
@@ -4017,6 +4105,10 @@ int persistent_blocks_on(int ncu) {
   return ncu * per;
 }
 
+// the backward kernels' launches (defined at the end of the file)
+void launch_init_back(const InitArgs<StaticBG>& a, unsigned grid, hipStream_t st);
+void launch_run_back(const RunArgs<StaticBG>& a, unsigned grid, hipStream_t st);
+
 // solver construction / ray loop launchers shared by the static and the
 // time-varying entry points
 template <class BG>
@@ -4032,6 +4124,12 @@ rwrt_status launch_init(const BG& B, int64_t nray, const double* d_y0, const rwr
     return check_launch("hipMemsetAsync(summary)");
   if (nray == 0) return RWRT_OK;
   InitArgs<BG> a{B, nray, d_y0, p->rtol, p->atol, p->nt, d_state, d_count, d_nanrow, d_live, d_summary};
+  if constexpr (std::is_same<BG, StaticBG>::value) {
+    if (p->flags & RWRT_PARAMS_BACKWARD) {
+      launch_init_back(a, grid_for(nray, 256), (hipStream_t)stream);
+      return check_launch("rk45_init_back_kernel");
+    }
+  }
   hipLaunchKernelGGL(rk45_init_kernel<BG>, dim3(grid_for(nray, 256)), dim3(256), 0,
                      (hipStream_t)stream, a);
   return check_launch("rk45_init_kernel");
@@ -4234,6 +4332,8 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   // heavy_blocks blocks either way; none for the fp32-arithmetic variant)
   if (n_heavy > 0 && std::is_void<typename TvBlock<BG>::type>::value && !std::is_same<BG, StaticBG>::value)
     return fail(RWRT_ERR_ARG, "latency mode (n_heavy > 0) is not built for fp32-arithmetic levels%s");
+  // (check_flags: only the static entries come here with the flag)
+  const bool backward = std::is_same<BG, StaticBG>::value && (p->flags & RWRT_PARAMS_BACKWARD) != 0;
   // the context's settings are read once, under its lock: a concurrent
   // rwrt_ctx_set_latency_density cannot change the density between sizing the
   // latency-mode grid and launching it
@@ -4294,7 +4394,10 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   }
   if (nray > n_heavy || team_blocks) {
     const int64_t grid = team_blocks + (nray > n_heavy ? blocks : 0);
-    if (a.trace && std::is_same<BG, StaticBG>::value) {
+    if (backward) {
+      // (the forward kernels' grid: same launch bounds and LDS; the diagnostic trace is the forward kernels')
+      if constexpr (std::is_same<BG, StaticBG>::value) launch_run_back(a, (unsigned)grid, st);
+    } else if (a.trace && std::is_same<BG, StaticBG>::value) {
       if constexpr (std::is_same<BG, StaticBG>::value) {
         hipLaunchKernelGGL((rk45_run_kernel<BG, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
         hipLaunchKernelGGL((rk45_run_kernel<BG, true, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
@@ -4305,7 +4408,7 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
       if constexpr (std::is_same<BG, StaticBG>::value)
         hipLaunchKernelGGL((rk45_run_kernel<BG, false, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
     }
-    if (rwrt_status s = check_launch("rk45_run_kernel")) return s;
+    if (rwrt_status s = check_launch(backward ? "rk45_run_back_kernel" : "rk45_run_kernel")) return s;
   }
   if (d_tail_from)
     hipLaunchKernelGGL(frozen_tail_kernel<BG>, dim3((unsigned)((nray + kFillThreads - 1) / kFillThreads)),
@@ -4781,6 +4884,7 @@ rwrt_status rwrt_rk45_init(const rwrt_grid* g, const double* d_packed, int64_t n
                            const double* d_y0, const rwrt_params* p, double* d_state,
                            int64_t* d_count, int32_t* d_nanrow, int32_t* d_live,
                            int64_t* d_summary, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_init", p, true)) return s;
   Field F;
   if (rwrt_status s = make_field(g, d_packed, F)) return s;
   return launch_init(StaticBG{F}, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary,
@@ -4792,6 +4896,7 @@ rwrt_status rwrt_rk45_run(rwrt_ctx* ctx, const rwrt_grid* g, const double* d_pac
                           int32_t it_begin, int32_t it_end, const int64_t* d_order,
                           int64_t n_heavy, double* d_state, int64_t* d_count, int32_t* d_nanrow,
                           double* d_out, int32_t* d_work, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_run", p, true)) return s;
   return rwrt_rk45_run_tails(ctx, g, d_packed, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state,
                              d_count, d_nanrow, d_out, nullptr, nullptr, d_work, stream);
 }
@@ -4802,6 +4907,7 @@ rwrt_status rwrt_rk45_run_tails(rwrt_ctx* ctx, const rwrt_grid* g, const double*
                                 int64_t n_heavy, double* d_state, int64_t* d_count, int32_t* d_nanrow,
                                 double* d_out, int32_t* d_tail_from, double* d_tail_row, int32_t* d_work,
                                 void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_run_tails", p, true)) return s;
   Field F;
   if (rwrt_status s = make_field(g, d_packed, F)) return s;
   return launch_run(ctx, StaticBG{F}, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state,
@@ -4814,6 +4920,7 @@ rwrt_status rwrt_rk45_run_slots(rwrt_ctx* ctx, const rwrt_grid* g, const double*
                                 int64_t n_heavy, double* d_state, int64_t* d_count, int32_t* d_nanrow,
                                 double* d_out, const int32_t* d_row_slot, int32_t* d_tail_from,
                                 double* d_tail_row, int32_t* d_work, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_run_slots", p, true)) return s;
   if (!d_row_slot) return fail(RWRT_ERR_ARG, "rwrt_rk45_run_slots needs d_row_slot%s");
   Field F;
   if (rwrt_status s = make_field(g, d_packed, F)) return s;
@@ -4870,6 +4977,7 @@ rwrt_status rwrt_rk45_init_tv(const rwrt_grid* g, const rwrt_background* b, int6
                               const double* d_y0, const rwrt_params* p, double* d_state,
                               int64_t* d_count, int32_t* d_nanrow, int32_t* d_live,
                               int64_t* d_summary, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_init_tv", p, false)) return s;
   if (b && b->fp32 == 2) {
     VaryingBGA32 B;
     if (rwrt_status s = make_varying(g, b, static_cast<VaryingBG<float>&>(B))) return s;
@@ -4890,6 +4998,7 @@ rwrt_status rwrt_rk45_run_tv(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_backg
                              int32_t it_end, const int64_t* d_order, int64_t n_heavy,
                              double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
                              int32_t* d_work, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_run_tv", p, false)) return s;
   return rwrt_rk45_run_tv_tails(ctx, g, b, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state,
                                 d_count, d_nanrow, d_out, nullptr, nullptr, d_work, stream);
 }
@@ -4929,6 +5038,7 @@ rwrt_status rwrt_rk45_run_tv_tails(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt
                                    int32_t it_begin, int32_t it_end, const int64_t* d_order, int64_t n_heavy,
                                    double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
                                    int32_t* d_tail_from, double* d_tail_row, int32_t* d_work, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_run_tv_tails", p, false)) return s;
   return run_tv(ctx, g, b, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count, d_nanrow,
                 d_out, d_tail_from, d_tail_row, d_work, stream, nullptr);
 }
@@ -4939,6 +5049,7 @@ rwrt_status rwrt_rk45_run_tv_slots(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt
                                    double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
                                    const int32_t* d_row_slot, int32_t* d_tail_from, double* d_tail_row,
                                    int32_t* d_work, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_run_tv_slots", p, false)) return s;
   if (!d_row_slot) return fail(RWRT_ERR_ARG, "rwrt_rk45_run_tv_slots needs d_row_slot%s");
   return run_tv(ctx, g, b, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count, d_nanrow,
                 d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
@@ -4948,6 +5059,7 @@ rwrt_status rwrt_rk45_init_stack(const rwrt_grid* g, const rwrt_stack* stack, in
                                  const double* d_y0, const rwrt_params* p, double* d_state,
                                  int64_t* d_count, int32_t* d_nanrow, int32_t* d_live,
                                  int64_t* d_summary, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_init_stack", p, false)) return s;
   StackBG B;
   if (rwrt_status s = make_stack(g, stack, nray, B)) return s;
   return launch_init(B, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream);
@@ -4959,6 +5071,7 @@ rwrt_status rwrt_rk45_run_stack(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_st
                                 double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
                                 const int32_t* d_row_slot, int32_t* d_tail_from, double* d_tail_row,
                                 int32_t* d_work, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_run_stack", p, false)) return s;
   StackBG B;
   if (rwrt_status s = make_stack(g, stack, nray, B)) return s;
   return launch_run(ctx, B, nray, p, d_tbound, it_begin, it_end, d_order, 0, d_state, d_count, d_nanrow,
@@ -5013,6 +5126,7 @@ rwrt_status rwrt_rk4_run(rwrt_ctx* ctx, const rwrt_grid* g, const double* d_pack
                          int64_t nray, const rwrt_params* p, int32_t it_begin, int32_t it_end,
                          const int64_t* d_order, double* d_state, int64_t* d_count,
                          int32_t* d_nanrow, double* d_out, int32_t* d_work, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk4_run", p, false)) return s;
   Field F;
   if (rwrt_status s = ctx_check(ctx)) return s;
   if (rwrt_status s = make_field(g, d_packed, F)) return s;
@@ -5131,3 +5245,15 @@ rwrt_status rwrt_host_fill_rows(double* dst, int64_t nrows, int64_t ncol, int64_
 }
 
 }  // extern "C"
+
+// The backward kernels' launches, last in the file (see rk45_init_back_kernel).
+namespace rwrt {
+void launch_init_back(const InitArgs<StaticBG>& a, unsigned grid, hipStream_t st) {
+  hipLaunchKernelGGL(rk45_init_back_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+}
+// both tiers: the launch's verdict ends one of the two at its entry (as forward)
+void launch_run_back(const RunArgs<StaticBG>& a, unsigned grid, hipStream_t st) {
+  hipLaunchKernelGGL(rk45_run_back_kernel<false>, dim3(grid), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(rk45_run_back_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+}
+}  // namespace rwrt

@@ -44,6 +44,7 @@ class RunResult:
         self.break_row = break_row  # wr.py:853-855 global early exit (None = no break)
         self.n_live = n_live
         self.bounds = []            # the [it_begin, it_end) row windows launched
+        self.backward = False       # rows at -t_eval (integrate(backward=True))
 
     @property
     def ray_steps(self):
@@ -419,13 +420,31 @@ class RayEngine:
 
     # ------------------------------------------------------------ ray loop
     @staticmethod
-    def params(nt, tstep, rtol=1e-6, atol=1e-6, msf=1e-3, cut_off=0.1, cut_rad=None):
-        """``rwrt_params`` exactly as WR / RK45 derive them."""
+    def params(nt, tstep, rtol=1e-6, atol=1e-6, msf=1e-3, cut_off=0.1, cut_rad=None, backward=False):
+        """``rwrt_params`` exactly as WR / RK45 derive them.  ``backward``: the
+        loop's direction is -1 (``RWRT_PARAMS_BACKWARD``); ``min_step`` and the
+        cut-off use the interval's magnitude either way."""
         rtol = max(rtol, 100 * np.finfo(np.float64).eps)          # rkf45.py:21-26
         tstep = float(tstep)
         min_step = min(msf * tstep, (tstep - 0) * 0.001)          # rkf45.py:362, wr.py:792-794
         cut = cut_off * tstep / 3600.0 if cut_rad is None else float(cut_rad)   # wr.py:170
-        return H.Params(rtol, atol, min_step, cut, int(nt), 0, tstep)
+        return H.Params(rtol, atol, min_step, cut, int(nt), H.PARAMS_BACKWARD if backward else 0, tstep)
+
+    @staticmethod
+    def is_backward(p):
+        return bool(p.flags & H.PARAMS_BACKWARD)
+
+    def _check_backward(self, group=None, stop_row=None):
+        """What backward tracing does not have, refused before any launch: it is
+        the static basic state's DP5(4) loop on one device, start to end."""
+        if self.bg is not None:
+            raise NotImplementedError("backward tracing runs on a static basic state (no time-varying levels)")
+        if self.nmember:
+            raise NotImplementedError("backward tracing has no member stacks")
+        if group is not None:
+            raise NotImplementedError("backward tracing is not sharded over a process group")
+        if stop_row is not None:
+            raise NotImplementedError("backward tracing has no checkpoints (stop_row)")
 
     def member_tensor(self, member, nray):
         """The per-ray member indices of a stack engine as the int32 device
@@ -451,6 +470,8 @@ class RayEngine:
     def init(self, y0, p, member=None):
         """Solver construction on the GPU; returns the per-ray state tensors
         (a member-stack engine: with each ray's ``member``, which ``take`` carries)."""
+        if self.is_backward(p):
+            self._check_backward()
         y0 = torch.as_tensor(y0, dtype=F64, device=self.device).contiguous()
         nray = y0.shape[1]
         if self.nmember:
@@ -634,6 +655,8 @@ class RayEngine:
         with ``tails`` (a ``Tails``) the frozen rays' constant rows go there instead;
         with ``slots`` (a ``Slots`` computed on ``st``) ``out`` holds the live
         rays' row blocks only."""
+        if self.is_backward(p):
+            self._check_backward()
         lib = H.load()
         ctx = self.ctx
         if self.bg is not None:
@@ -681,14 +704,17 @@ class RayEngine:
                                            H.dptr(tails.row, F64), H.dptr(view, F64), self._stream()))
 
     def integrate_rk4(self, y0, nt, tstep, cut_off=0.1, chunk=None, sink=None, out=None,
-                      cut_rad=None, events=None, group=None):
+                      cut_rad=None, events=None, group=None, backward=False):
         """The fixed-step RK4 ray loop (wr.py:702-765) for ``y0[5, nray]``.
 
         Same chunked ``sink`` protocol as ``integrate``; the nacc column and
         ``RunResult.nacc`` count RK4 steps taken, ``nrej`` steps held because a
         stage input was masked (the ray keeps its state, wr.py:609-618; a masked
         first stage holds it for every remaining step, each counted).
+        ``backward`` is refused: the RK4 loop has no signed step.
         """
+        if backward:
+            raise NotImplementedError("backward tracing is the DP5(4) loop's (integrate); the RK4 loop has no signed step")
         if self.bg is not None or self.nmember:
             raise NotImplementedError("the RK4 loop runs on the reference's static basic state")
         p = self.params(nt, tstep, cut_off=cut_off, cut_rad=cut_rad)
@@ -729,8 +755,16 @@ class RayEngine:
 
     def integrate(self, y0, nt, tstep, rtol=1e-6, atol=1e-6, msf=1e-3, cut_off=0.1,
                   ttotal=None, chunk=None, sink=None, out=None, cut_rad=None, events=None,
-                  group=None, order_policy="priority", first_chunk=None, team=0, stop_row=None, member=None):
+                  group=None, order_policy="priority", first_chunk=None, team=0, stop_row=None, member=None,
+                  backward=False):
         """The whole ray loop for ``y0[5, nray]``; rows 1..nt-1 go to ``sink``.
+
+        ``backward``: the rays are traced to negative time (the reference's
+        stepper with direction = -1): row ``i`` is the state at ``-t_eval[i]``,
+        every column as forward (ug, vg: the true group velocity there).  A
+        static basic state only; no ``stop_row``, no ``group``.  Every
+        schedule option (chunks, orders, ``team``, the hand-off, the row
+        layouts) applies and changes no bit.
 
         ``member`` (a member-stack engine, ``from_levels(members=True)``): the
         member each ray lives in, ``[nray]`` integers in ``[0, nmember)``; such
@@ -753,7 +787,9 @@ class RayEngine:
         failure and the all-NaN early exit -- are decided over every rank, so a
         sharded run equals the single-GPU run.  Returns a ``RunResult``.
         """
-        p = self.params(nt, tstep, rtol, atol, msf, cut_off, cut_rad)
+        if backward:
+            self._check_backward(group, stop_row)
+        p = self.params(nt, tstep, rtol, atol, msf, cut_off, cut_rad, backward=backward)
         y0 = torch.as_tensor(y0, dtype=F64, device=self.device).contiguous()
         nray = y0.shape[1]
         if self.nmember:
@@ -773,7 +809,9 @@ class RayEngine:
         if n_live > 0 and n_finite == 0:
             # rkf45.py:423-425: at the first step every live column has a NaN
             # h_abs -> status -1 -> wr.py:886-887 breaks before storing row 1.
-            return RunResult(cnt[:, 0], cnt[:, 1], st["nanrow"], True, 1, n_live)
+            res = RunResult(cnt[:, 0], cnt[:, 1], st["nanrow"], True, 1, n_live)
+            res.backward = bool(backward)
+            return res
         return self.advance(st, p, tb, 1, chunk=chunk, sink=sink, out=out, events=events,
                             group=group, order_policy=order_policy, first_chunk=first_chunk,
                             n_live=n_live, n_live_local=n_live_local, team=team, stop_row=stop_row)
@@ -839,7 +877,10 @@ class RayEngine:
         rejected, at the start of an earlier launch) orders the first launch
         longest-first by the attempts since; otherwise live rays go first.
         ``split`` ("auto", see SPLIT_RHO) may split the launch after the
-        leading ones once more."""
+        leading ones once more.  The direction is ``p``'s (``params(backward=)``:
+        ``tb`` stays the non-negative elapsed times)."""
+        if self.is_backward(p):
+            self._check_backward(group, stop_row)
         if self.nmember:
             self._check_stack_run(team, group)
             if "member" not in st:
@@ -966,6 +1007,7 @@ class RayEngine:
         res.bounds = bounds
         res.state, res.next_row = st, end
         res.params = run_params(p, tb)
+        res.backward = self.is_backward(p)
         return res
 
     def _check_stack_run(self, team, group):
@@ -989,6 +1031,8 @@ class RayEngine:
         st = res.state
         if "member" in st:
             raise NotImplementedError("member stacks have no checkpoints")
+        if getattr(res, "backward", False):
+            raise NotImplementedError("backward tracing has no checkpoints")
         return {"state": st["state"].cpu().numpy(), "count": st["count"].cpu().numpy(),
                 "nanrow": st["nanrow"].cpu().numpy(), "next_row": np.int64(res.next_row),
                 "params": np.asarray(res.params, np.float64), "nray": np.int64(st["nray"])}
@@ -1014,10 +1058,13 @@ class RayEngine:
 
     def resume(self, ck, nt, tstep, rtol=1e-6, atol=1e-6, msf=1e-3, cut_off=0.1, ttotal=None,
                chunk=None, sink=None, out=None, cut_rad=None, events=None, group=None,
-               order_policy="priority", first_chunk=None, team=0, stop_row=None):
+               order_policy="priority", first_chunk=None, team=0, stop_row=None, backward=False):
         """Rows ``[ck['next_row'], nt)`` of the run a checkpoint was taken from
         (the same ``nt``, ``tstep`` and tolerances), into ``sink`` as in
-        ``integrate``: the rows and counters equal an uninterrupted run's."""
+        ``integrate``: the rows and counters equal an uninterrupted run's.
+        (Forward runs only: a checkpoint does not record the direction.)"""
+        if backward:
+            raise NotImplementedError("backward tracing has no checkpoints (resume)")
         if self.nmember:
             raise NotImplementedError("member stacks have no checkpoints")
         p = self.params(nt, tstep, rtol, atol, msf, cut_off, cut_rad)

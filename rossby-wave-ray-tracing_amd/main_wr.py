@@ -2,6 +2,8 @@
 
 Identical keys and flow; the ray loop runs on the GPU (``mode='hip'``,
 ``inte_method='rk45'``).  Files: netCDF-3 or ``.npz`` (see ncio.py).
+One optional key beyond the reference's: ``backward`` (default False) traces
+the rays from the sources towards negative time (``WR(backward=True)``).
 """
 import warnings
 
@@ -36,7 +38,7 @@ parameters = {
 
 def real2d_hnf(nzwn, mm, nn, freq, zwn, inputuv, ncfile, bsfile, SW_lon, SW_lat, dlon, dlat,
                nnx, nny, mode, tstep, ttotal, xcyclic, root_method, read_dtype, cal_dtype,
-               inte_method, atol, rtol, MinStepFactor):
+               inte_method, atol, rtol, MinStepFactor, backward=False):
     """Read the basic flow, trace every ray, write the results (main_wr.py:31-89)."""
     from constants import hour, day
     from wr import WR
@@ -44,7 +46,7 @@ def real2d_hnf(nzwn, mm, nn, freq, zwn, inputuv, ncfile, bsfile, SW_lon, SW_lat,
     nsource = nnx * nny
     wr1 = WR(nzwn, nsource, tstep * hour, ttotal * day, freq, nx=mm, ny=nn,
              read_dtype=read_dtype, cal_dtype=cal_dtype, rtol=rtol, atol=atol,
-             ncfile=inputuv, MinStepFactor=MinStepFactor)
+             ncfile=inputuv, MinStepFactor=MinStepFactor, backward=backward)
     wr1.bs.loadbs_ncfile(inputuv)
     wr1.bs.ready(xcyclic=xcyclic)
     if bsfile:

@@ -36,7 +36,7 @@ class WR:
     def __init__(self, nzwn, nsource, tstep=1. * hour, ttotal=20. * day, freq=0,
                  cal_dtype="float64", read_dtype="float32", rtol=1e-6, atol=1e-6,
                  cut_off=0.1, nx=None, ny=None, ncfile=None, MinStepFactor=1e-3,
-                 chunk_rows=None, progress=False):
+                 chunk_rows=None, progress=False, backward=False):
         if cal_dtype != "float64":
             raise ValueError("cal_dtype must be 'float64' (as in main_wr.py:21)")
         self.all_dtype = cal_dtype
@@ -63,6 +63,11 @@ class WR:
         self.chunk_rows = chunk_rows
         self.progress = progress
         self.last_run = None       # engine.RunResult of the last ray_run
+        # backward ray tracing: the sources are receptors, the rays are
+        # integrated towards negative time (the RK45 loop's direction = -1) and
+        # row i of the history is the state at -i * tstep (rows index elapsed
+        # steps; ug, vg are the true group velocity at the point)
+        self.backward = bool(backward)
 
     def get_defualt_nlon_and_nlat(self, ncfile):
         """(nlat, nlon) from the file's lat/lon (or u's last two dims), wr.py:173-212."""
@@ -222,12 +227,12 @@ class WR:
             if method == "rk4":
                 res = eng.integrate_rk4(torch.as_tensor(y0[:, idx]), self.nt, float(self.tstep[0]),
                                         chunk=chunk, sink=sink, cut_rad=float(self.cut_off[0]),
-                                        group=grp, out=out)
+                                        group=grp, out=out, backward=self.backward)
             else:
                 res = eng.integrate(torch.as_tensor(y0[:, idx]), self.nt, float(self.tstep[0]),
                                     self.rtol, self.atol, self.MinStepFactor, ttotal=self.ttotal,
                                     chunk=chunk, sink=sink, cut_rad=float(self.cut_off[0]),
-                                    group=grp, out=out)
+                                    group=grp, out=out, backward=self.backward)
         finally:
             if hs is not None:
                 hs.finish()
@@ -274,6 +279,7 @@ class WR:
         key = mode + "_rk45" if inte_method == "rk45" else mode
         if key not in SUPPORTED:
             self.core_ray_run(key)     # raises before any work
+        self._check_direction(key)
         self.ray_initial(mode=mode, root_method=root_method)
         rank, world = shard.world_info(group) if group is not None else (0, 1)
         product, sink = make(rank, self.bs.engine().device)
@@ -491,6 +497,12 @@ class WR:
 
         return self._reduce_on_device(make, mode, inte_method, group, root_method)
 
+    def _check_direction(self, key):
+        """Backward tracing is the RK45 loop's: the RK4 loop is refused before any work."""
+        if self.backward and key != "hip_rk45":
+            raise NotImplementedError("backward ray tracing needs ray_run(mode='hip', inte_method='rk45'): "
+                                      "the fixed-step RK4 loop has no signed step")
+
     def core_ray_run(self, mode="hip_rk45", group=None):
         if mode not in SUPPORTED:
             raise NotImplementedError(
@@ -511,6 +523,7 @@ class WR:
         key = mode + "_rk45" if inte_method == "rk45" else mode
         if key not in SUPPORTED:
             self.core_ray_run(key)     # raises before any work
+        self._check_direction(key)
         self.ray_initial(mode=mode, root_method=root_method)   # wr.py:900 (mode 'hip': GPU)
         if debug and debug_file is not None:
             try:
