@@ -43,9 +43,10 @@ extern "C" {
                                   (rwrt_ray_arrival), the basic-state diagnostics
                                   (rwrt_bs_diag), the wave-ray flux maps
                                   (rwrt_ray_flux), the residence-time maps along ray
-                                  segments (rwrt_ray_track) and the gate-crossing maps
-                                  (rwrt_ray_cross): no earlier signature or layout
-                                  changed */
+                                  segments (rwrt_ray_track), the gate-crossing maps
+                                  (rwrt_ray_cross) and the WKB phase along rays with its
+                                  wave-field maps (rwrt_ray_phase): no earlier signature
+                                  or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -756,6 +757,80 @@ rwrt_status rwrt_ray_cross(const rwrt_cross_map* m, int64_t nray,
                            double* d_prev, int64_t* d_cnt, double* d_tsum,
                            double* d_wsum, int64_t* d_dropped,
                            int32_t* d_ncross, double* d_tfirst, void* stream);
+
+/* ABI 5, additive: the WKB phase along rays and wave-field maps.  A WKB wave
+ * is A exp(i theta); the ray loops integrate A (the amp column) and the local
+ * wavenumbers k, l, this integrates the phase theta = int k dlon + l dY along
+ * every ray, dY = dlat / cos(lat) (k, l: the Mercator wavenumbers times the
+ * earth's radius, as the rows carry them), and superposes the rays' waves per
+ * map box.  The definition is phase.reference_phase (NumPy);
+ * csrc/phase_rows.h restates it.
+ *
+ * A row is valid iff lon, lat, k and l are finite, |lat| < pi/2 (the double
+ * nearest pi/2, compared in fp64) and the columns need / wcol, where named,
+ * are finite; for a valid row a = l / cos(lat).  Segment i joins rows i-1 and
+ * i and is joined iff both are valid and the ray's channel c is in
+ * [0, nchan); then, one rounding per operation, in this order, no FMA:
+ *   dk = (0.5 * (k0 + k1)) * (lon1 - lon0)
+ *   dl = (0.5 * (a0 + a1)) * (lat1 - lat0)
+ *   theta_i = theta_{i-1} + (dk + dl);  nseg += 1
+ * else theta_i = theta_{i-1}.  Every valid row i (row 0 too) of a ray whose
+ * channel is in range has psi = theta_i - omega_dt * (double)i and is binned
+ * as rwrt_ray_density bins it (lam = (lon % 2 pi) % 2 pi, wrapped axis); a
+ * binned row with a finite psi adds cnt += 1, re += w cos(psi), im += w
+ * sin(psi), wabs += |w| (w: the column wcol, 1 without one, and then there is
+ * no wabs); a binned row whose psi is not finite adds 1 to dropped and nothing
+ * else. */
+typedef struct {
+  int32_t nx, ny, nchan;
+  int32_t need, wcol;       /* row columns, -1 (none) or 2..6: must be finite / weighs the deposit */
+  int32_t reserved;
+  double lat0, inv_dlat;    /* rad; ny / (lat1 - lat0) */
+  double inv_dlon;          /* nx / (2 pi) */
+  double omega_dt;          /* the wave's frequency times the row interval, rad per row */
+} rwrt_phase_map;           /* 56 bytes */
+
+/* Integrates the phase over the segments that end on rows it_begin <= i <
+ * it_end of nray rays and deposits those rows: ACCUMULATES into d_cnt (int64),
+ * d_re, d_im and d_wabs (fp64; d_wabs NULL iff wcol < 0), each
+ * [nchan][ny][nx], d_dropped[1] (int64) and, per ray column, d_theta (fp64)
+ * and d_nseg (int32), each [nacc_cols].  The caller zeroes the maps, d_nseg
+ * and d_dropped and writes theta_0 into d_theta and NaN into d_carry once, so
+ * time chunks and shards add up.  Row layouts, d_ray and d_chan (indexed by
+ * column) are those of rwrt_ray_track; a ray whose channel is outside
+ * [0, nchan) is not walked and its columns stay.
+ *  d_carry[4][nacc_cols] (fp64): the carried previous row of every ray -- lon
+ *    (NaN: no valid previous row), lat, k and a.  A running state, like
+ *    d_prev of rwrt_ray_track: the calls for one ray deliver CONSECUTIVE rows
+ *    in order, once.  A call with it_begin == 0 treats its first row as row 0
+ *    whatever d_carry holds: it sets the carry, deposits, and leaves theta as
+ *    given.
+ * One lane walks one ray: one cos per valid row (a is carried, not
+ * recomputed), one sincos per deposit (the device library's), one 64-bit
+ * integer add and two or three hardware fp64 adds per deposit, no
+ * compare-exchange loop; the ray's own columns of d_theta, d_nseg and d_carry
+ * take plain loads and stores.  A constant tail of n rows is its first row
+ * plus n - 1 segments of length zero: nseg += n - 1, theta takes the one sum
+ * (dk + dl) of such a segment (+0, or NaN where an average overflows), and the
+ * n - 1 equal deposits are made as ONE product (double)(n - 1) * term per sum
+ * when omega_dt == 0, row by row otherwise.  cnt, nseg and dropped are exact;
+ * theta follows the definition's order of operations and differs from it only
+ * through cos; re, im and wabs depend on the arrival order in their last bits.
+ * RWRT_ERR_ARG before any HIP call: a NULL map, d_carry, d_theta, d_nseg,
+ * d_cnt, d_re, d_im or d_dropped; d_wabs present without wcol or missing with
+ * it; nx, ny or nchan not positive; nchan*ny*nx >= 2^31; need or wcol outside
+ * {-1, 2..6}; inv_dlon or inv_dlat not finite and positive; lat0 or omega_dt
+ * not finite; it_begin < 0; nacc_cols not covering the rays; the row
+ * arguments as for rwrt_ray_density.  Asynchronous and ordered on `stream`;
+ * needs no rwrt_ctx.  nray == 0 is a no-op. */
+rwrt_status rwrt_ray_phase(const rwrt_phase_map* m, int64_t nray,
+                           int32_t it_begin, int32_t it_end,
+                           const double* d_rows, const int32_t* d_row_slot,
+                           const int32_t* d_tail_from, const double* d_tail_row,
+                           const int64_t* d_ray, int64_t nacc_cols, const int32_t* d_chan,
+                           double* d_carry, double* d_theta, int32_t* d_nseg,
+                           int64_t* d_cnt, double* d_re, double* d_im, double* d_wabs,
+                           int64_t* d_dropped, void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

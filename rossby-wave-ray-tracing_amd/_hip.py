@@ -22,7 +22,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
                "rwrt_launch_plan_bytes", "rwrt_launch_plan",
                "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival", "rwrt_ray_flux",
-               "rwrt_ray_track", "rwrt_ray_cross",
+               "rwrt_ray_track", "rwrt_ray_cross", "rwrt_ray_phase",
                "rwrt_wn_map", "rwrt_wn_fill",
                "rwrt_sh_filter",
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
@@ -131,6 +131,19 @@ class CrossMapC(ctypes.Structure):
 
 assert ctypes.sizeof(CrossGateC) == 32 and ctypes.sizeof(CrossMapC) == 288
 
+
+class PhaseMapC(ctypes.Structure):
+    """``rwrt_phase_map``: the map a ``rwrt_ray_phase`` call deposits into
+    (``need`` / ``wcol``: row columns, -1 for none; ``omega_dt``: radians per
+    row)."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nchan", ctypes.c_int32),
+                ("need", ctypes.c_int32), ("wcol", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("lat0", ctypes.c_double), ("inv_dlat", ctypes.c_double), ("inv_dlon", ctypes.c_double),
+                ("omega_dt", ctypes.c_double)]
+
+
+assert ctypes.sizeof(PhaseMapC) == 56
+
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
 NDIAG = 23     # RWRT_NDIAG: the planes of rwrt_bs_diag
 
@@ -167,6 +180,7 @@ def load():
     F = ctypes.POINTER(FluxMapC)
     T = ctypes.POINTER(TrackMapC)
     X = ctypes.POINTER(CrossMapC)
+    Ph = ctypes.POINTER(PhaseMapC)
     sig = {
         "rwrt_pack_fields": [G, _P, _P, _P],
         "rwrt_mercator_point": [G, _P, _I64, _P, _P, _P, _P],
@@ -190,6 +204,7 @@ def load():
         "rwrt_ray_flux": [F, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_track": [T, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_cross": [X, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+        "rwrt_ray_phase": [Ph, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_summary": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, R, _P, _P, _P],
         "rwrt_wn_map": [G, _P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_wn_fill": [_I32, _I32, _I32, _I32, _P, _P, _P],

@@ -222,7 +222,14 @@ class EnsembleWR:
         ``make(device, chan, nray) -> (product, sink)`` (any raymap product;
         ``chan``: each ray slot's channel under ``by``, an int32 array or
         None).  ``make`` also hands row 0 (``self.rlon[0]`` ..) to the
-        product.  Returns the product; only row 0 of the history is filled."""
+        product.  Returns the product; only row 0 of the history is filled.
+        One wave-field map per member (phase.py)::
+
+            def make(device, chan, nray):
+                m = PhaseMap(with_channels(spec, ew.nmember), nray, device, chan)
+                m.start(ew.rlon[0], ew.rlat[0], ew.ramp[0], ew.ramp[0], k=ew.rzwn[0], l=ew.rmwn[0])
+                return m, PhaseSink(m)
+        """
         chan, _ = self.channels(by)
         self.ray_initial()
         product, sink = make(self.engine().device, chan, self.nray)

@@ -1,9 +1,9 @@
 """What the products that reduce a launch's rows on the device share.
 
-The ray-density, arrival-time, flux, residence-time and gate-crossing maps
-(density.py, arrival.py, flux.py, track.py, cross.py) and the per-ray
-summaries (summary.py) each have a kernel, a NumPy reference and device arrays
-of their own.  Around those they are the same, and that part is here, once:
+The ray-density, arrival-time, flux, residence-time, gate-crossing and
+wave-field maps (density.py, arrival.py, flux.py, track.py, cross.py, phase.py)
+and the per-ray summaries (summary.py) each have a kernel, a NumPy reference
+and device arrays of their own.  Around those they are the same, and that part is here, once:
 
   ``GridSpec``      the lon-lat grid of a spec: its validation and the factors
                     of the index arithmetic (``LatBand``: the latitude part;

@@ -414,9 +414,11 @@ class WR:
 
         return self._reduce_on_device(make, mode, inte_method, group, root_method)
 
-    def _ray_segments(self, reference, Map, Sink, spec, mode, inte_method, by, group, root_method):
-        """``ray_track`` / ``ray_cross``: the product's reference function,
-        its ``raymap.CarriedMap`` and its sink."""
+    def _ray_segments(self, reference, Map, Sink, spec, mode, inte_method, by, group, root_method, start=None):
+        """``ray_track`` / ``ray_cross`` / ``ray_phase``: the product's
+        reference function, its ``raymap.CarriedMap`` and its sink.  ``start(m,
+        rank)``: hands row 0 to the map where ``CarriedMap.start``'s columns
+        are not all it needs."""
         spec, chan = self._channels(spec, by)
         if mode == "numpy":
             return reference(self._history_rows(inte_method, root_method, group), chan, spec)
@@ -424,7 +426,10 @@ class WR:
         def make(rank, device):
             m = Map(spec, 3 * self.nsource * self.nzwn, device, chan)
             # row 0 on every rank: the rank that integrates a ray carries it into row 1
-            m.start(self.rlon[0], self.rlat[0], self._column(spec.ncol), self._column(spec.wcol))
+            if start is None:
+                m.start(self.rlon[0], self.rlat[0], self._column(spec.ncol), self._column(spec.wcol))
+            else:
+                start(m, rank)
             return m, Sink(m)
 
         return self._reduce_on_device(make, mode, inte_method, group, root_method)
@@ -463,6 +468,39 @@ class WR:
         sum over the ranks."""
         import cross as X
         return self._ray_segments(X.reference_cross, X.CrossMap, X.CrossSink, spec, mode, inte_method, by, group, root_method)
+
+    def ray_phase(self, spec, mode="hip", inte_method="rk45", by=None, group=None, root_method="numpy"):
+        """Initialise and integrate all rays like ``ray_run``, but integrate
+        the WKB phase ``theta = int k dlon + l dY`` along every ray and
+        deposit every ray point's wave ``w exp(i psi)`` into its box of a
+        lon-lat map (phase.py) instead of delivering the history: returns the
+        ``phase.PhaseMap`` -- per box ``cnt``, ``re``, ``im`` and, with
+        ``spec.weight``, ``wabs`` (``field()``, ``amplitude()``,
+        ``mean_phase()``, ``coherence()``), and per ray ``theta`` and
+        ``nseg``, arrays that reshape to ``(3, nsource, nzwn)``; only row 0 of
+        ``rlon .. rvg`` is filled.
+
+        ``spec``: a ``phase.PhaseSpec``; where it leaves ``omega_dt`` at 0 and
+        this run's ``freq`` is not 0, ``omega_dt = freq * tstep``, negated for
+        ``backward=True`` (row i is the state at ``-i * tstep`` there).  ``by``:
+        as in ``ray_density``.  ``mode='numpy'`` integrates on the GPU all the
+        same, delivers the history and applies ``phase.reference_phase`` on the
+        host (small runs; returns its dict).  With a process ``group`` every
+        rank ends with the sum over the ranks."""
+        from dataclasses import replace
+        import phase as P
+        if spec.omega_dt == 0.0 and float(self.freq[0]) != 0.0:
+            omega_dt = float(self.freq[0]) * float(self.tstep[0])
+            spec = replace(spec, omega_dt=-omega_dt if self.backward else omega_dt)
+
+        def start(m, rank):
+            m.start(self.rlon[0], self.rlat[0], self._column(m.spec.ncol), self._column(m.spec.wcol),
+                    k=self.rzwn[0], l=self.rmwn[0])
+            if rank != 0:
+                m.clear_maps()     # (row 0 is deposited once: by rank 0)
+
+        return self._ray_segments(P.reference_phase, P.PhaseMap, P.PhaseSink, spec, mode, inte_method, by, group,
+                                  root_method, start=start)
 
     def ray_summary(self, regions=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but reduce every
