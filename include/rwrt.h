@@ -148,8 +148,17 @@ rwrt_status rwrt_ctx_set_latency_density(rwrt_ctx* ctx, int32_t rays_per_wave);
  * one bracketing level, exchanged by v_permlane32_swap -- no HBM gathers
  * while a ray stays in its cell and level pair, half the LDS-DMA per refill;
  * RayEngine's default, C5 fp64 1.21 -> 1.61e9 with the other round-5 changes).
- * Schedule only: results do not depend on it (ABI 3). */
+ * Schedule only: results do not depend on it (ABI 3).  The release-stack
+ * entry (rwrt_rk45_run_rel, below) honours it too; it reads the setting itself
+ * when it launches, where the time-varying entries read it before. */
 rwrt_status rwrt_ctx_set_tv_lanes(rwrt_ctx* ctx, int32_t lanes);
+/* The work-queue grid of this context's last DP5(4) ray-loop launch (additive
+ * within ABI 5; diagnostic): the persistent blocks that pulled rays from the
+ * queue (0 before any launch, and for a launch whose rays all ran in latency
+ * mode) and the rays a block holds at once (256; 128 at 32 rays per wave), so
+ * blocks * rays_per_block rays are in flight and any further live ray is a
+ * lane's second.  Host bookkeeping only: no HIP call. */
+rwrt_status rwrt_ctx_last_grid(rwrt_ctx* ctx, int32_t* blocks, int32_t* rays_per_block);
 /* Drain-time hand-off of this context's static-state ray loops (ABI 4): once
  * a call's work queue is drained, a wavefront with at most max_rays rays left
  * (0 = off, at most 16; default 16) continues them four lanes per ray, in the
@@ -995,6 +1004,47 @@ rwrt_status rwrt_rk45_run_stack(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_st
                                 double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
                                 const int32_t* d_row_slot, int32_t* d_tail_from, double* d_tail_row,
                                 int32_t* d_work, void* stream);
+/* Release stacks (additive members of ABI 5): rays released at different
+ * times into ONE time-varying background in one launch -- the same sources
+ * every day of a season, or at the start, middle and end of a regime
+ * transition.  The background is rwrt_background's (nlev fp64 levels at
+ * t0 + j * dt); d_t0[ray] is that ray's own value of rwrt_background.t0, and
+ * b->t0 is ignored.  A ray's time starts at 0 as in every time-varying call,
+ * so a ray released r seconds after the first level has d_t0[ray] =
+ * (time of the first level) - r, and its row i is its state i * tstep after
+ * its release.  Past the last level the last level persists, before the first
+ * the first.
+ *
+ * The level index and weight of an evaluation at ray time t are those of
+ * rwrt_rk45_run_tv with t0 = d_t0[ray]: s = (t - d_t0[ray]) / dt and the same
+ * clamps.  Nothing else differs, so a ray's rows, counters and state are bit
+ * for bit what rwrt_rk45_init_tv / rwrt_rk45_run_tv{,_tails,_slots} of the
+ * same build give for that ray alone with b->t0 = d_t0[ray], whatever the
+ * other rays, the queue order, the row layout, the chunking or
+ * rwrt_ctx_set_tv_lanes.
+ *
+ * What release stacks do not have: the latency mode (there is no n_heavy),
+ * fp32 level storage and the fp32 RHS (b->fp32 must be 0), the backward
+ * direction, RK4.
+ *
+ * The one run entry covers the three row layouts: d_row_slot, d_tail_from and
+ * d_tail_row may be NULL under the rules of rwrt_rk45_run_stack.  Every other
+ * argument is as in rwrt_rk45_init_tv / rwrt_rk45_run_tv_slots.  RWRT_ERR_ARG
+ * before any HIP call, with a message that starts with the entry's name: a
+ * NULL grid or background, nlev < 1, dt <= 0, b->fp32 != 0, NULL d_t0 with
+ * nray > 0, RWRT_PARAMS_BACKWARD or any other flag bit; and, with the
+ * messages they have there, every check of rwrt_rk45_run_tv_slots (NULL ctx,
+ * params, levels, row window, buffers, alignment, slots without tails).
+ * nray == 0 launches nothing. */
+rwrt_status rwrt_rk45_init_rel(const rwrt_grid* g, const rwrt_background* b, const double* d_t0,
+                               int64_t nray, const double* d_y0, const rwrt_params* p, double* d_state,
+                               int64_t* d_count, int32_t* d_nanrow, int32_t* d_live, int64_t* d_summary,
+                               void* stream);
+rwrt_status rwrt_rk45_run_rel(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_background* b, const double* d_t0,
+                              int64_t nray, const rwrt_params* p, const double* d_tbound, int32_t it_begin,
+                              int32_t it_end, const int64_t* d_order, double* d_state, int64_t* d_count,
+                              int32_t* d_nanrow, double* d_out, const int32_t* d_row_slot, int32_t* d_tail_from,
+                              double* d_tail_row, int32_t* d_work, void* stream);
 /* Stepper known-answer tests: the same device stepper on the analytic ODEs of
  * the rkf45.py demos (rkf45.py:839-882), driven like rk45_simple_current
  * (rkf45.py:672-724).  kind: 0 dx/dt = 2t, 1 dx/dt = e^(0.1 t), 2 Lorenz

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("RWRT_LIB", os.path.join(_HERE, "librwrt.so"))
 NFIELD_REF, NFIELD_PACK, NVAR, NMERC, NOUT, NSTATE = 18, 12, 5, 12, 8, 12
 ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_destroy",
                "rwrt_ctx_set_latency_density", "rwrt_ctx_set_tv_lanes", "rwrt_ctx_set_handoff",
-               "rwrt_ctx_set_trace",
+               "rwrt_ctx_set_trace", "rwrt_ctx_last_grid",
                "rwrt_pack_fields",
                "rwrt_mercator_point", "rwrt_rhs", "rwrt_dp54_attempt",
                "rwrt_ray_initial", "rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails",
@@ -28,6 +28,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
                "rwrt_rk45_run_tv_slots", "rwrt_rhs_tv",
                "rwrt_rk45_init_stack", "rwrt_rk45_run_stack",
+               "rwrt_rk45_init_rel", "rwrt_rk45_run_rel",
                "rwrt_kat_rk45", "rwrt_selftest_math", "rwrt_host_fill_rows")
 
 RWRT_OK, RWRT_ERR_ARG, RWRT_ERR_HIP, RWRT_SOLVER_FAILED = 0, 1, 2, 3
@@ -220,12 +221,15 @@ def load():
         "rwrt_rk45_init_stack": [G, ctypes.POINTER(Stack), _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
         "rwrt_rk45_run_stack": [_P, G, ctypes.POINTER(Stack), _I64, Pr, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P, _P],
+        "rwrt_rk45_init_rel": [G, B, _P, _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
+        "rwrt_rk45_run_rel": [_P, G, B, _P, _I64, Pr, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ctx_create": [_I32, ctypes.POINTER(_P)],
         "rwrt_ctx_destroy": [_P],
         "rwrt_ctx_set_latency_density": [_P, _I32],
         "rwrt_ctx_set_tv_lanes": [_P, _I32],
         "rwrt_ctx_set_handoff": [_P, _I32],
         "rwrt_ctx_set_trace": [_P, _P, _I64],
+        "rwrt_ctx_last_grid": [_P, ctypes.POINTER(_I32), ctypes.POINTER(_I32)],
         "rwrt_rhs_tv": [G, B, _I64, _P, _P, _P, _P],
         "rwrt_kat_rk45": [_I32, _I64, _P, _I32, _P, _D, _D, _D, _P, _P],
         "rwrt_selftest_math": [_I32, _I64, _P, _P, _P, _P],
@@ -308,6 +312,14 @@ class Context:
         if getattr(self, "_hof", 16) != int(max_rays):
             check(load().rwrt_ctx_set_handoff(self._h, int(max_rays)))
             self._hof = int(max_rays)
+
+    def last_grid(self):
+        """``(blocks, rays_per_block)`` of the last ray-loop launch's work-queue
+        grid (rwrt_ctx_last_grid): ``blocks * rays_per_block`` rays are in flight
+        at once, any further live ray is some lane's second."""
+        b, r = _I32(), _I32()
+        check(load().rwrt_ctx_last_grid(self._h, ctypes.byref(b), ctypes.byref(r)))
+        return int(b.value), int(r.value)
 
     def set_trace(self, trace=None):
         """Diagnostic ray trace (rwrt_ctx_set_trace): ``trace`` an int64 device

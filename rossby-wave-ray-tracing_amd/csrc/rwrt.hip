@@ -577,8 +577,14 @@ __device__ __forceinline__ void lookup_end(const CachedStaticBG& B, const Cached
 // 0x9800 to 0x9f100 bytes).  The block shrank from 0x1FEA00 by the 0x1140
 // bytes: .text stays at 0x213f00 and every kernel of the parent at its
 // address (profiles/backward/device_asm_identity.txt).
+// The four release-stack kernels (rk45_init_kernel, rk45_run_kernel,
+// frozen_tail_kernel, frozen_fill_kernel <ReleaseBG>) are first instantiated
+// from the last functions of this file too and lie behind the backward ones;
+// they added 0x1700 bytes in front of .text (symbols, metadata, four kernel
+// descriptors), which the block gave up: 0x1FD8C0 -> 0x1FC1C0, .text stays at
+// 0x213f00 (profiles/release/device_asm_identity.txt).
 #ifndef RWRT_PLACEMENT_PAD
-#define RWRT_PLACEMENT_PAD 0x1FD8C0
+#define RWRT_PLACEMENT_PAD 0x1FC1C0
 #endif
 __device__ __attribute__((used)) static const char kPlacementPad[RWRT_PLACEMENT_PAD] = {1};
 
@@ -1084,6 +1090,60 @@ __device__ __forceinline__ void lookup_end(const PairVaryingBG64& B, const PairV
   B.end(p, g);
 }
 
+// A release stack (include/rwrt.h rwrt_rk45_run_rel): ONE time-varying fp64
+// background and one level origin per ray, t0_of[ray] -- the ray's own value of
+// rwrt_background.t0, so that ray time 0 is the ray's release time.  A ray's
+// arithmetic is the time-varying path's with that t0: at(ray) IS that
+// VaryingBG<double> (the direct reads: the init kernel, the row-end ugvg_at,
+// frozen_row), and the two cached forms below are CachedVaryingBG64 and
+// PairVaryingBG64 whose V.t0 pull() sets when the lane takes a ray (per lane: a
+// VGPR pair where the plain loop holds a scalar).  Nothing else differs:
+// level() forms s = (t - t0) / dt from it with the same operations and clamps.
+// Unlike CachedStackBG::pull, the held (cell, level pair) key is NOT dropped:
+// every ray reads the one levels array, and the key names a cell and a level
+// index j of it, so two rays with different t0 that come to the same cell and
+// the same j read the same bytes -- the slice the previous ray left is this
+// ray's too (the weight wt is recomputed on every lookup, never cached).
+struct ReleaseBG {
+  static constexpr bool kTimeVarying = true;
+  VaryingBG<double> V;               // V.t0 unused
+  const double* t0_of = nullptr;     // [nray]
+  __device__ __forceinline__ VaryingBG<double> at(int64_t ray) const {
+    VaryingBG<double> R = V;
+    R.t0 = t0_of[ray];
+    return R;
+  }
+};
+__device__ __forceinline__ VaryingBG<double> ray_bg(const ReleaseBG& B, int64_t ray) { return B.at(ray); }
+
+// (wrappers, not derived types: the generic lookup_begin(const BG&) would take
+// a derived type before the base's overload; C is mutable for pull() as
+// CachedStackBG::moff is)
+struct CachedReleaseBG64 {
+  static constexpr bool kTimeVarying = true;
+  mutable CachedVaryingBG64 C;
+  __device__ __forceinline__ void pull(const ReleaseBG& B, int64_t ray) const { C.V.t0 = B.t0_of[ray]; }
+  __device__ __forceinline__ void interp4(double lon, double lat, double t, double& fu, double& fv,
+                                          double& fqx, double& fqy) const {
+    C.V.interp4(lon, lat, t, fu, fv, fqx, fqy);
+  }
+};
+__device__ __forceinline__ CachedVaryingBG64::Pending lookup_begin(const CachedReleaseBG64& B, double lon,
+                                                                   double lat, double t) {
+  return B.C.begin(lon, lat, t);
+}
+__device__ __forceinline__ void lookup_end(const CachedReleaseBG64& B,
+                                           const CachedVaryingBG64::Pending& p, double g[11]) {
+  B.C.end(p, g);
+}
+// (both lanes of a pair hold the same ray -- run_rays hands the lower lane's
+// queue position to the upper one -- so both read the same t0_of[ray])
+struct PairReleaseBG64 {
+  static constexpr bool kTimeVarying = true;
+  mutable PairVaryingBG64 C;
+  __device__ __forceinline__ void pull(const ReleaseBG& B, int64_t ray) const { C.V.t0 = B.t0_of[ray]; }
+};
+
 // Latency mode of the time-varying ray loops (rk45_run_kernel's first
 // heavy_blocks blocks, run_rays<.., kReplica>): ONE ray per wavefront,
 // replicated on all 64 lanes (the same state and the same operations on every
@@ -1251,6 +1311,14 @@ struct LaneBG<VaryingBG<double>> {
   __device__ static CachedVaryingBG64 make(const VaryingBG<double>& B, char* lds) {
     const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     return CachedVaryingBG64{B, lds + wave * kCacheBytesPerWave, (threadIdx.x & 63u) * 16u, ~0u, ~0u, -1};
+  }
+};
+template <>
+struct LaneBG<ReleaseBG> {
+  using type = CachedReleaseBG64;
+  static constexpr int kLdsBytes = 4 * kCacheBytesPerWave;
+  __device__ static CachedReleaseBG64 make(const ReleaseBG& B, char* lds) {
+    return CachedReleaseBG64{LaneBG<VaryingBG<double>>::make(B.V, lds)};
   }
 };
 
@@ -2378,6 +2446,14 @@ template <class P>
 struct IsPair : std::false_type {};
 template <>
 struct IsPair<RayProblemT<PairVaryingBG64>> : std::true_type {};
+template <>
+struct IsPair<RayProblemT<PairReleaseBG64>> : std::true_type {};
+// (a release stack's pair: the attempt of the lane's PairVaryingBG64, whose t0 pull() set)
+__device__ __forceinline__ double pair_attempt(const PairReleaseBG64& B, const KShared<5>& K5, double t,
+                                               const double* y, const double* f, double h, double rtol,
+                                               double atol, double* ynew, double* k6, double* aux) {
+  return pair_attempt(B.C, K5, t, y, f, h, rtol, atol, ynew, k6, aux);
+}
 
 // select_initial_step (rkf45.py:34-99); kBack: direction = -1 (the trial point
 // lies at t0 - h0, y0 - h0 f0; d0, d1, d2 are even in the sign)
@@ -2594,6 +2670,11 @@ __global__ void rk45_init_kernel(InitArgs<BG> a) {
       const RayProblemT<StaticBG> Pm{ray_bg(a.B, i)};
       Pm(0.0, y, f);
       habs = initial_step(Pm, 0.0, y, f, a.rtol, a.atol);
+    } else if constexpr (std::is_same<BG, ReleaseBG>::value) {   // the time-varying problem at the ray's own t0
+      (void)P;
+      const RayProblemT<VaryingBG<double>> Pr{ray_bg(a.B, i)};
+      Pr(0.0, y, f);
+      habs = initial_step(Pr, 0.0, y, f, a.rtol, a.atol);
     } else {
       P(0.0, y, f);                                   // RungeKutta.__init__: f = fun(t, y)
       habs = initial_step(P, 0.0, y, f, a.rtol, a.atol);
@@ -3302,6 +3383,8 @@ __device__ __forceinline__ void run_rays(const RunArgs<BG>& a, const LBG& lbg, c
       }
       // (a member stack: the lane's lookups now go to this ray's member)
       if constexpr (std::is_same<LBG, CachedStackBG>::value) P.B.pull(a.B, ray);
+      // (a release stack: the lane's level origin is now this ray's; the held cell stays -- ReleaseBG)
+      if constexpr (std::is_same<BG, ReleaseBG>::value) P.B.pull(a.B, ray);
 #pragma unroll
       for (int v = 0; v < 5; ++v) {
         L.y[v] = a.state[v * a.nray + ray];
@@ -3520,6 +3603,13 @@ rk45_run_kernel(RunArgs<BG> a) {
     if (a.B.half) {   // (kernel-uniform) 32 rays per wave: lane pairs
 #endif
       run_rays<BG, PairVaryingBG64, false, false, true>(a, PairVaryingBG64::make(a.B, smem + kKBytes), smem, -1);
+      return;
+    }
+  }
+  if constexpr (std::is_same<BG, ReleaseBG>::value) {   // a release stack's lane pairs
+    if (a.B.V.half) {   // (kernel-uniform)
+      run_rays<BG, PairReleaseBG64, false, false, true>(
+          a, PairReleaseBG64{PairVaryingBG64::make(a.B.V, smem + kKBytes)}, smem, -1);
       return;
     }
   }
@@ -4150,7 +4240,8 @@ struct rwrt_ctx {
   int device = 0;
   int ncu = 256;
   int blocks_static = 0, blocks_f32 = 0, blocks_f64 = 0, blocks_a32 = 0;   // persistent grids
-  int blocks_stack = 0;
+  int blocks_stack = 0, blocks_rel = 0;
+  int last_blocks = 0, last_block_rays = 0;   // the queue grid of the last ray-loop launch (rwrt_ctx_last_grid)
   uint8_t* flags = nullptr;
   size_t cap = 0;
   char* img = nullptr;         // cache image of the static state (cache_image_kernel), rebuilt per call
@@ -4269,6 +4360,7 @@ template <> int& ctx_blocks<VaryingBG<float>>(rwrt_ctx* c) { return c->blocks_f3
 template <> int& ctx_blocks<VaryingBG<double>>(rwrt_ctx* c) { return c->blocks_f64; }
 template <> int& ctx_blocks<VaryingBGA32>(rwrt_ctx* c) { return c->blocks_a32; }
 template <> int& ctx_blocks<StackBG>(rwrt_ctx* c) { return c->blocks_stack; }
+template <> int& ctx_blocks<ReleaseBG>(rwrt_ctx* c) { return c->blocks_rel; }
 
 template <class BG>
 int ctx_persistent_blocks(rwrt_ctx* c) {
@@ -4356,7 +4448,14 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   // persistent block): the persistent grid shrinks by as many CUs
   if (team_blocks) blocks = std::max<int64_t>(1, blocks - team_blocks * (blocks / ctx->ncu));
   int64_t block_rays = 256;   // rays a block runs at once
-  if constexpr (BG::kTimeVarying) block_rays = B.half ? 128 : 256;
+  // (a release stack: the context's rays per wave, read here under its lock -- the entry has not looked at ctx)
+  bool rel_half = false;
+  if constexpr (std::is_same<BG, ReleaseBG>::value) {
+    rel_half = ctx->tv_lanes == 32;
+    block_rays = rel_half ? 128 : 256;
+  } else if constexpr (BG::kTimeVarying) {
+    block_rays = B.half ? 128 : 256;
+  }
   const int64_t need = (nray - n_heavy + block_rays - 1) / block_rays;
   if (blocks > need) blocks = need;
   RunArgs<BG> a{B, nray, p->rtol, p->atol, p->min_step, p->cut_off, p->nt, it_begin, it_end,
@@ -4364,6 +4463,7 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
                 n_heavy, 0, haversine_cut(p->cut_off), nullptr};
   a.row_slot = d_row_slot;
   a.handoff = handoff;
+  if constexpr (std::is_same<BG, ReleaseBG>::value) a.B.V.half = rel_half;
   // frozen rays: flagged on `stream`, filled on the context's side stream
   // while the run kernel (which skips them) integrates the rest; `stream` then
   // waits for the fill, so the call stays one stream-ordered operation.  With
@@ -4392,6 +4492,8 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
     a.trace = ctx->trace;
     a.trace_cap = ctx->trace ? ctx->trace_cap : 0;
   }
+  ctx->last_blocks = nray > n_heavy ? (int)blocks : 0;
+  ctx->last_block_rays = (int)block_rays;
   if (nray > n_heavy || team_blocks) {
     const int64_t grid = team_blocks + (nray > n_heavy ? blocks : 0);
     if (backward) {
@@ -4758,6 +4860,15 @@ rwrt_status rwrt_ctx_set_tv_lanes(rwrt_ctx* c, int32_t lanes) {
   if (lanes != 32 && lanes != 64) return fail(RWRT_ERR_ARG, "time-varying lanes per wave must be 32 or 64%s");
   std::lock_guard<std::mutex> lock(c->mu);
   c->tv_lanes = lanes;
+  return RWRT_OK;
+}
+
+rwrt_status rwrt_ctx_last_grid(rwrt_ctx* ctx, int32_t* blocks, int32_t* rays_per_block) {
+  if (rwrt_status s = ctx_check(ctx)) return s;
+  if (!blocks || !rays_per_block) return fail(RWRT_ERR_ARG, "rwrt_ctx_last_grid: NULL output%s");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  *blocks = ctx->last_blocks;
+  *rays_per_block = ctx->last_block_rays;
   return RWRT_OK;
 }
 
@@ -5256,4 +5367,52 @@ void launch_run_back(const RunArgs<StaticBG>& a, unsigned grid, hipStream_t st) 
   hipLaunchKernelGGL(rk45_run_back_kernel<false>, dim3(grid), dim3(256), 0, st, a);
   hipLaunchKernelGGL(rk45_run_back_kernel<true>, dim3(grid), dim3(256), 0, st, a);
 }
+
+// a release stack from the ABI description: every check that needs no HIP call
+// (b->t0 is ignored: d_t0 replaces it)
+static rwrt_status make_release(const char* fn, const rwrt_grid* g, const rwrt_background* b, const double* d_t0,
+                                int64_t nray, ReleaseBG& B) {
+  if (!g) return fail(RWRT_ERR_ARG, "%s: grid is NULL", fn);
+  if (!b) return fail(RWRT_ERR_ARG, "%s: background is NULL", fn);
+  if (b->nlev < 1) return fail(RWRT_ERR_ARG, "%s: background needs nlev >= 1", fn);
+  if (!(b->dt > 0.0)) return fail(RWRT_ERR_ARG, "%s: background level spacing dt must be > 0", fn);
+  if (b->fp32 != 0) return fail(RWRT_ERR_ARG, "%s: a release stack takes fp64 levels only (background.fp32 must be 0)", fn);
+  if (nray > 0 && !d_t0) return fail(RWRT_ERR_ARG, "%s: d_t0 is NULL", fn);
+  B = ReleaseBG{};
+  if (rwrt_status s = make_varying(g, b, B.V)) return s;
+  B.V.t0 = 0.0;
+  B.t0_of = d_t0;
+  return RWRT_OK;
+}
 }  // namespace rwrt
+
+// The release-stack entries, after every other launch of the file: their
+// kernels (rk45_init_kernel<ReleaseBG>, rk45_run_kernel<ReleaseBG>,
+// frozen_fill_kernel / frozen_tail_kernel<ReleaseBG>) are first instantiated
+// from here, so the compiler emits them behind every other kernel of the code
+// object and none of those moves ("Code placement" above).
+extern "C" {
+using namespace rwrt;
+
+rwrt_status rwrt_rk45_init_rel(const rwrt_grid* g, const rwrt_background* b, const double* d_t0, int64_t nray,
+                               const double* d_y0, const rwrt_params* p, double* d_state, int64_t* d_count,
+                               int32_t* d_nanrow, int32_t* d_live, int64_t* d_summary, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_init_rel", p, false)) return s;
+  ReleaseBG B;
+  if (rwrt_status s = make_release("rwrt_rk45_init_rel", g, b, d_t0, nray, B)) return s;
+  return launch_init(B, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream);
+}
+
+rwrt_status rwrt_rk45_run_rel(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_background* b, const double* d_t0,
+                              int64_t nray, const rwrt_params* p, const double* d_tbound, int32_t it_begin,
+                              int32_t it_end, const int64_t* d_order, double* d_state, int64_t* d_count,
+                              int32_t* d_nanrow, double* d_out, const int32_t* d_row_slot, int32_t* d_tail_from,
+                              double* d_tail_row, int32_t* d_work, void* stream) {
+  if (rwrt_status s = check_flags("rwrt_rk45_run_rel", p, false)) return s;
+  ReleaseBG B;
+  if (rwrt_status s = make_release("rwrt_rk45_run_rel", g, b, d_t0, nray, B)) return s;
+  return launch_run(ctx, B, nray, p, d_tbound, it_begin, it_end, d_order, 0, d_state, d_count, d_nanrow, d_out,
+                    d_tail_from, d_tail_row, d_work, stream, d_row_slot);
+}
+
+}  // extern "C"

@@ -354,11 +354,18 @@ class RayEngine:
             rows, info = torch.stack([r for r, _ in per]), torch.stack([i for _, i in per]).sum(0)
         else:
             rows, info = self.initial_rows_dev(src, self.zwn_tensor(zwn, freq))
-        if check and int(info.item()) != 0:
+        if check:
+            self.check_initial(info)
+        return rows
+
+    @staticmethod
+    def check_initial(info):
+        """Raise like ``np.linalg.eigvals`` in the reference when ``info`` (the
+        counter of ``initial_rows_dev``; waited for here) is not zero."""
+        if int(info.item()) != 0:
             raise np.linalg.LinAlgError(
                 f"Array must not contain infs or NaNs ({int(info.item())} dispersion "
                 f"polynomials with non-finite coefficients; np.roots raises here too)")
-        return rows
 
     # ----------------------------------------------------- wavenumber map
     levels = None   # the levels.Levels of an engine built from_levels
@@ -446,6 +453,39 @@ class RayEngine:
         if stop_row is not None:
             raise NotImplementedError("backward tracing has no checkpoints (stop_row)")
 
+    def _check_release(self, team=0, group=None, stop_row=None, backward=False):
+        """What a release stack (``release=``) does not have, refused before any
+        launch: it is the fp64 time-varying DP5(4) loop on one device, start to end."""
+        if self.nmember:
+            raise NotImplementedError("release stacks have no member stacks (an engine built from_levels(members=True))")
+        if self.bg is None:
+            raise ValueError("release= needs a time-varying engine (from_levels with more than one level, "
+                             "or time_varying=True)")
+        if self.bg.fp32:
+            raise NotImplementedError("release stacks need fp64 level storage (no fp32 levels, no fp32 RHS)")
+        if backward:
+            raise NotImplementedError("release stacks have no backward tracing")
+        if isinstance(team, (list, tuple)) or team != 0:
+            raise ValueError("release stacks have no latency mode: team / n_heavy must be 0")
+        if group is not None:
+            raise NotImplementedError("release stacks are not sharded over a process group")
+        if stop_row is not None:
+            raise NotImplementedError("release stacks have no checkpoints (stop_row, checkpoint, resume)")
+
+    def release_t0(self, release, nray):
+        """Each ray's level origin ``levels.t0 - release`` (fp64, formed on the
+        host) as the device tensor the release kernels read; ``release``: ``nray``
+        finite seconds after the first level (tensor or array).  ``ValueError``
+        for a wrong length, NaN or inf."""
+        r = release.detach().cpu().numpy() if torch.is_tensor(release) else release
+        r = np.asarray(r, dtype=np.float64).reshape(-1)
+        if r.size != nray:
+            raise ValueError(f"release has {r.size} entries for {nray} rays")
+        if not np.isfinite(r).all():
+            raise ValueError("release times must be finite (seconds after the first level)")
+        from levels import level_origin
+        return torch.as_tensor(level_origin(self.levels.t0, r), dtype=F64).to(self.device).contiguous()
+
     def member_tensor(self, member, nray):
         """The per-ray member indices of a stack engine as the int32 device
         tensor the kernels read; ``ValueError`` for a wrong length or an index
@@ -467,13 +507,18 @@ class RayEngine:
         return H.Stack(H.dptr(pk, F64, "packed members"), self.nmember, 0, pk.stride(0),
                        H.dptr(st["member"], torch.int32, "member"))
 
-    def init(self, y0, p, member=None):
+    def init(self, y0, p, member=None, release=None):
         """Solver construction on the GPU; returns the per-ray state tensors
-        (a member-stack engine: with each ray's ``member``, which ``take`` carries)."""
+        (a member-stack engine: with each ray's ``member``, which ``take`` carries;
+        with ``release``, seconds after the first level per ray: with each ray's
+        level origin ``t0``, which ``take`` carries too -- ``integrate``)."""
+        if release is not None:
+            self._check_release(backward=self.is_backward(p))
         if self.is_backward(p):
             self._check_backward()
         y0 = torch.as_tensor(y0, dtype=F64, device=self.device).contiguous()
         nray = y0.shape[1]
+        t0 = None if release is None else self.release_t0(release, nray)
         if self.nmember:
             member = self.member_tensor(member, nray)
         elif member is not None:
@@ -492,6 +537,13 @@ class RayEngine:
             fn, bg = lib.rwrt_rk45_init_stack, ctypes_ref(stack)
         elif self.bg is None:
             fn, bg = lib.rwrt_rk45_init, H.dptr(self.packed)
+        elif t0 is not None:
+            st["t0"] = t0
+            H.check(lib.rwrt_rk45_init_rel(self.grid, ctypes_ref(self.bg), H.dptr(t0, F64, "t0"), nray, H.dptr(y0),
+                                           ctypes_ref(p), H.dptr(st["state"]), H.dptr(st["count"]),
+                                           H.dptr(st["nanrow"]), H.dptr(st["live"]), H.dptr(st["summary"]),
+                                           self._stream()))
+            return st
         else:
             fn, bg = lib.rwrt_rk45_init_tv, ctypes_ref(self.bg)
         H.check(fn(self.grid, bg, nray, H.dptr(y0), ctypes_ref(p), H.dptr(st["state"]),
@@ -657,6 +709,8 @@ class RayEngine:
         rays' row blocks only."""
         if self.is_backward(p):
             self._check_backward()
+        if "t0" in st:
+            self._check_release(team=n_heavy, backward=self.is_backward(p))
         lib = H.load()
         ctx = self.ctx
         if self.bg is not None:
@@ -675,6 +729,16 @@ class RayEngine:
                 ctx.handle, self.grid, ctypes_ref(stack), st["nray"], ctypes_ref(p), H.dptr(tbound, F64),
                 int(it_begin), int(it_end), H.dptr(order, torch.int64), H.dptr(st["state"]), H.dptr(st["count"]),
                 H.dptr(st["nanrow"]), H.dptr(out, F64), None if slots is None else H.dptr(slots.slot, torch.int32),
+                None if tails is None else H.dptr(tails.frm, torch.int32),
+                None if tails is None else H.dptr(tails.row, F64), H.dptr(self.work), self._stream()))
+            return
+        if "t0" in st:
+            # a release stack: one entry for the three row layouts; no latency mode
+            H.check(lib.rwrt_rk45_run_rel(
+                ctx.handle, self.grid, ctypes_ref(self.bg), H.dptr(st["t0"], F64, "t0"), st["nray"], ctypes_ref(p),
+                H.dptr(tbound, F64), int(it_begin), int(it_end), H.dptr(order, torch.int64), H.dptr(st["state"]),
+                H.dptr(st["count"]), H.dptr(st["nanrow"]), H.dptr(out, F64),
+                None if slots is None else H.dptr(slots.slot, torch.int32),
                 None if tails is None else H.dptr(tails.frm, torch.int32),
                 None if tails is None else H.dptr(tails.row, F64), H.dptr(self.work), self._stream()))
             return
@@ -704,7 +768,7 @@ class RayEngine:
                                            H.dptr(tails.row, F64), H.dptr(view, F64), self._stream()))
 
     def integrate_rk4(self, y0, nt, tstep, cut_off=0.1, chunk=None, sink=None, out=None,
-                      cut_rad=None, events=None, group=None, backward=False):
+                      cut_rad=None, events=None, group=None, backward=False, release=None):
         """The fixed-step RK4 ray loop (wr.py:702-765) for ``y0[5, nray]``.
 
         Same chunked ``sink`` protocol as ``integrate``; the nacc column and
@@ -713,6 +777,8 @@ class RayEngine:
         first stage holds it for every remaining step, each counted).
         ``backward`` is refused: the RK4 loop has no signed step.
         """
+        if release is not None:
+            raise NotImplementedError("release stacks are the DP5(4) loop's (integrate); the RK4 loop has none")
         if backward:
             raise NotImplementedError("backward tracing is the DP5(4) loop's (integrate); the RK4 loop has no signed step")
         if self.bg is not None or self.nmember:
@@ -756,8 +822,18 @@ class RayEngine:
     def integrate(self, y0, nt, tstep, rtol=1e-6, atol=1e-6, msf=1e-3, cut_off=0.1,
                   ttotal=None, chunk=None, sink=None, out=None, cut_rad=None, events=None,
                   group=None, order_policy="priority", first_chunk=None, team=0, stop_row=None, member=None,
-                  backward=False):
+                  backward=False, release=None):
         """The whole ray loop for ``y0[5, nray]``; rows 1..nt-1 go to ``sink``.
+
+        ``release`` (a time-varying fp64 engine): seconds after the first level
+        at which each ray is released, ``[nray]`` finite values.  A ray's time
+        still starts at 0: its level origin is ``levels.t0 - release`` (the
+        state dict's ``t0``), so its row ``i`` is its state ``i * tstep`` after
+        its release, and its rows, counters and state are bit for bit those of
+        a time-varying engine on the same levels with ``t0 = levels.t0 -
+        release`` for that ray alone.  ``team=0`` only, no ``group``, no
+        ``stop_row``, no ``backward``; the two global outcomes are over all
+        rays of the call (``ensemble.member_outcomes`` decides them per release).
 
         ``backward``: the rays are traced to negative time (the reference's
         stepper with direction = -1): row ``i`` is the state at ``-t_eval[i]``,
@@ -787,6 +863,8 @@ class RayEngine:
         failure and the all-NaN early exit -- are decided over every rank, so a
         sharded run equals the single-GPU run.  Returns a ``RunResult``.
         """
+        if release is not None:
+            self._check_release(team, group, stop_row, backward)
         if backward:
             self._check_backward(group, stop_row)
         p = self.params(nt, tstep, rtol, atol, msf, cut_off, cut_rad, backward=backward)
@@ -797,7 +875,7 @@ class RayEngine:
             if stop_row is not None:
                 raise NotImplementedError("member stacks have no checkpoints (stop_row)")
         tb = torch.as_tensor(t_eval_of(nt, tstep, ttotal), dtype=F64, device=self.device)
-        st = self.init(y0, p, member)
+        st = self.init(y0, p, member, release)
         summary = st["summary"]
         n_live_local = int(summary[0].item())   # this rank's shard (the queue bound)
         if group is not None:
@@ -887,6 +965,8 @@ class RayEngine:
                 raise ValueError("a member-stack engine advances a state of its own init (st['member'])")
             if stop_row is not None:
                 raise NotImplementedError("member stacks have no checkpoints (stop_row)")
+        if "t0" in st:
+            self._check_release(team, group, stop_row, self.is_backward(p))
         nt = int(p.nt)
         end = nt if stop_row is None else max(int(start), min(int(stop_row), nt))
         nray = st["nray"]
@@ -1031,6 +1111,8 @@ class RayEngine:
         st = res.state
         if "member" in st:
             raise NotImplementedError("member stacks have no checkpoints")
+        if "t0" in st:
+            raise NotImplementedError("release stacks have no checkpoints")
         if getattr(res, "backward", False):
             raise NotImplementedError("backward tracing has no checkpoints")
         return {"state": st["state"].cpu().numpy(), "count": st["count"].cpu().numpy(),
@@ -1097,6 +1179,8 @@ class RayEngine:
                    nanrow=st["nanrow"][idx].contiguous(), nray=int(idx.numel()))
         if "member" in st:   # (a member stack's rays keep their member)
             sub["member"] = st["member"][idx].contiguous()
+        if "t0" in st:       # (a release stack's rays keep their level origin)
+            sub["t0"] = st["t0"][idx].contiguous()
         return sub
 
     @staticmethod

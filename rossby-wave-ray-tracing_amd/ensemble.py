@@ -77,7 +77,13 @@ class EnsembleResult:
 
 class EnsembleWR:
     """``WR`` over the members of a ``levels.Levels`` stack (fp64), one launch
-    for all members.  Same source and wavenumber setters as ``WR``."""
+    for all members.  Same source and wavenumber setters as ``WR``.
+
+    (``release.ReleaseWR`` is this class over another leading axis: ``axis``
+    names it -- the ``by=`` word, the output dimension -- and ``engine``,
+    ``ray_initial`` and ``_init`` are what differs.)"""
+
+    axis = "member"
 
     def __init__(self, levels, nzwn, nsource, tstep=1. * hour, ttotal=20. * day, freq=0, rtol=1e-6,
                  atol=1e-6, cut_off=0.1, MinStepFactor=1e-3, chunk_rows=None):
@@ -123,16 +129,16 @@ class EnsembleWR:
 
     def members(self):
         """Each ray slot's member, ``[nray]`` int32."""
-        return self.channels("member")[0]
+        return self.channels(self.axis)[0]
 
     def channels(self, by):
         """``(chan[nray] int32, nchan)`` of ``by``: 'member', 'zwn' or 'root';
         ``(None, 1)`` for None."""
         if by is None:
             return None, 1
-        axes = {"member": (0, self.nmember), "root": (1, 3), "zwn": (3, self.nzwn)}
+        axes = {self.axis: (0, self.nmember), "root": (1, 3), "zwn": (3, self.nzwn)}
         if by not in axes:
-            raise ValueError("by must be None, 'zwn', 'root' or 'member'")
+            raise ValueError(f"by must be None, 'zwn', 'root' or '{self.axis}'")
         ax, n = axes[by]
         shape = [1, 1, 1, 1]
         shape[ax] = n
@@ -155,13 +161,24 @@ class EnsembleWR:
             self._engine = RayEngine.from_levels(self.levels, members=True)
         return self._engine
 
+    def _initial_rows(self):
+        """Row 0 along the leading axis, a host array ``[nmember, 7, 3, nsource,
+        nzwn]`` (``RayEngine.initial_rows``: one ``rwrt_ray_initial`` call per member)."""
+        return self.engine().initial_rows(self.source_lon, self.source_lat, self.zwn, self.freq).cpu().numpy()
+
     def ray_initial(self):
-        """Row 0 of every member (``RayEngine.initial_rows``, one
-        ``rwrt_ray_initial`` call per member); the later rows are reset."""
-        rows = self.engine().initial_rows(self.source_lon, self.source_lat, self.zwn, self.freq).cpu().numpy()
+        """Row 0 of every member (``_initial_rows``); the later rows are reset."""
+        rows = self._initial_rows()
         for v, h in enumerate(self._allocate()):
             h[1:] = undef
             h[0] = rows[:, v]
+
+    def _init(self, eng, y0, p):
+        """``(st, member)``: the initialised state of every ray slot and each
+        slot's index along the leading axis (a device tensor)."""
+        import torch
+        st = eng.init(torch.as_tensor(y0), p, torch.as_tensor(self.members()))
+        return st, st["member"]
 
     def _run(self, sink, out=None, chunk=None):
         """Integrate every member's rays from row 0 into ``sink``."""
@@ -170,23 +187,22 @@ class EnsembleWR:
         eng = self.engine()
         hist = self._allocate()
         y0 = np.array([h[0] for h in hist[:5]], dtype=np.float64).reshape(5, self.nray)
-        member = torch.as_tensor(self.members())
         p = eng.params(self.nt, float(self.tstep[0]), self.rtol, self.atol, self.MinStepFactor,
                        cut_rad=float(self.cut_off[0]))
         tb = torch.as_tensor(t_eval_of(self.nt, float(self.tstep[0]), self.ttotal), dtype=F64, device=eng.device)
-        st = eng.init(torch.as_tensor(y0), p, member)
+        st, member = self._init(eng, y0, p)
         live = st["live"] != 0
-        failed, _ = member_outcomes(st["member"], live, st["state"][11], st["nanrow"], self.nmember, self.nt)
+        failed, _ = member_outcomes(member, live, st["state"][11], st["nanrow"], self.nmember, self.nt)
         if any(failed):
             # a failed member never steps (wr.py:886-887 breaks before row 1):
             # its rays are frozen here, so its counters stay 0
-            gone = torch.as_tensor(failed, device=eng.device)[st["member"].to(torch.int64)]
+            gone = torch.as_tensor(failed, device=eng.device)[member.to(torch.int64)]
             st["state"][:5, gone] = float("nan")
             live = live & ~gone
         n_live = int(live.sum().item())
         chunk = chunk or self.chunk_rows or _default_chunk(self.nray, self.nt)
         run = eng.advance(st, p, tb, 1, chunk=chunk, sink=sink, out=out, n_live=n_live, n_live_local=n_live)
-        _, break_row = member_outcomes(st["member"], st["live"], torch.zeros_like(st["state"][11]), st["nanrow"],
+        _, break_row = member_outcomes(member, st["live"], torch.zeros_like(st["state"][11]), st["nanrow"],
                                        self.nmember, self.nt)
         break_row = [1 if f else b for f, b in zip(failed, break_row)]
         self.last_run = EnsembleResult(run, failed, break_row, n_live)
@@ -270,15 +286,21 @@ class EnsembleWR:
         """``WR.output``'s variables with a ``member`` dimension."""
         import ncio
         self._allocate()
-        dims = {"zwn": self.nzwn, "source": self.nsource, "root": 3, "member": self.nmember, "time": self.nt}
-        full = ("time", "member", "root", "source", "zwn")
+        ax = self.axis
+        dims = {"zwn": self.nzwn, "source": self.nsource, "root": 3, ax: self.nmember, "time": self.nt}
+        full = ("time", ax, "root", "source", "zwn")
         v = {"zwn": (("zwn",), self.zwn),
              "source_index": (("source",), np.arange(self.nsource, dtype=np.int32)),
-             "member_index": (("member",), np.arange(self.nmember, dtype=np.int32)),
+             ax + "_index": ((ax,), np.arange(self.nmember, dtype=np.int32)),
              "time_index": (("time",), np.arange(self.nt, dtype=np.int32)),
              "rlon": (full, self.rlon * rad2deg, "degrees"),
              "rlat": (full, self.rlat * rad2deg, "degrees"),
              "rzwn": (full, self.rzwn, "rad_per_meter*Rearth"),
              "rmwn": (full, self.rmwn), "ramp": (full, self.ramp),
              "rug": (full, self.rug, "m s-1"), "rvg": (full, self.rvg, "m s-1")}
+        v.update(self._output_extra())
         ncio.write(ncfile, dims, v)
+
+    def _output_extra(self):
+        """Further variables of ``output`` (none here)."""
+        return {}

@@ -32,6 +32,26 @@ def trig_table(lat):
     return t
 
 
+def time_index(t, t0, dt, nlev):
+    """``(j, w)``: level index and weight of time ``t`` for levels at ``t0 + j*dt``
+    -- ``s = (t - t0) / dt``, ``j = clip(floor(s), 0, nlev - 2)`` (0 for one
+    level), ``w = min(max(s - j, 0), 1)``, in fp64 like the kernels."""
+    s = (np.float64(t) - np.float64(t0)) / np.float64(dt)
+    f = np.floor(s)
+    # (floor_i32: an index past int32 wraps to the most negative one, as NumPy's cast does)
+    i = -2 ** 31 if (f > 2147483647.0 or f != f) else int(max(f, -2147483648.0))
+    j = max(0, min(i, nlev - 2)) if nlev > 1 else 0
+    w = float(min(max(s - np.float64(j), np.float64(0.0)), np.float64(1.0)))
+    return j, w
+
+
+def level_origin(t0, release):
+    """A release stack's per-ray level origin: a ray released ``release``
+    seconds after the first level (valid at ``t0``) starts its own time at 0, so
+    its levels lie at ``(t0 - release) + j*dt``.  fp64, on the host."""
+    return np.float64(t0) - np.asarray(release, dtype=np.float64)
+
+
 class Levels:
     """``nlev`` basic states on one GPU, packed for the ray kernels."""
 
@@ -130,6 +150,38 @@ class Levels:
             from bsdiag import BSDiag
             self._diag = BSDiag.from_axes(self.lat, self.lon, self.dx, self.dy, self.device, self.lat_deg)
         return self._diag.compute(u, v, names, trunc=trunc)
+
+    def time_index(self, t):
+        """``(j, w)`` of ray time ``t`` (seconds, with ``t0`` as it stands): the
+        lower bracketing level and the weight of level ``j + 1``, by the
+        kernels' formulas and clamps (csrc/rwrt.hip VaryingBG::level)."""
+        return time_index(t, self.t0, self.dt, self.nlev)
+
+    def state_at(self, t):
+        """The fp64 packed state ``[ncol, nrow, 12]`` valid at ``t`` seconds
+        after the first level: ``P_j * (1 - w) + P_{j+1} * w`` with the kernels'
+        own ``j`` and ``w`` (``time_index``), as three separate tensor
+        operations (mul, mul, add: nothing contracts them).  ``packed[j]``
+        itself when ``w == 0.0`` and ``packed[j + 1]`` itself when ``w == 1.0``,
+        so a release at a level time starts from that level's own rows bit for
+        bit.  fp64 levels.  (``release.reference_state_at`` is the NumPy
+        definition.)
+
+        For ``0 < w < 1`` the initial rows' ``ug, vg`` come from this blended
+        state, while a run's RHS blends the two levels AFTER the bilinear
+        lookup in each: the two agree to rounding, not bit for bit."""
+        if self.fp32:
+            raise NotImplementedError("state_at needs fp64 level storage")
+        # (ray time 0 of a ray whose level origin is t0 - t: the kernels' s of its first evaluation)
+        j, w = time_index(0.0, np.float64(self.t0) - np.float64(t), self.dt, self.nlev)
+        up = j + 1 if self.nlev > 1 else j   # (one level: the kernels blend it with itself)
+        if w == 0.0:
+            return self.packed[j]
+        if w == 1.0:
+            return self.packed[up]
+        a = torch.mul(self.packed[j], 1.0 - w)
+        b = torch.mul(self.packed[up], w)
+        return torch.add(a, b)
 
     def background(self):
         """The ``rwrt_background`` description of these levels."""
