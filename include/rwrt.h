@@ -44,9 +44,9 @@ extern "C" {
                                   (rwrt_bs_diag), the wave-ray flux maps
                                   (rwrt_ray_flux), the residence-time maps along ray
                                   segments (rwrt_ray_track), the gate-crossing maps
-                                  (rwrt_ray_cross) and the WKB phase along rays with its
-                                  wave-field maps (rwrt_ray_phase): no earlier signature
-                                  or layout changed */
+                                  (rwrt_ray_cross), the WKB phase along rays with its
+                                  wave-field maps (rwrt_ray_phase) and the ray-tube maps
+                                  (rwrt_ray_tube): no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -840,6 +840,80 @@ rwrt_status rwrt_ray_phase(const rwrt_phase_map* m, int64_t nray,
                            double* d_carry, double* d_theta, int32_t* d_nseg,
                            int64_t* d_cnt, double* d_re, double* d_im, double* d_wabs,
                            int64_t* d_dropped, void* stream);
+
+/* ABI 5, additive: ray-tube maps -- geometric spreading, caustics and the
+ * Maslov index per ray.  The first consumer that reads more than one ray's
+ * rows per lane: ray j's tube is spanned by the difference vectors between its
+ * neighbours in the source lattice, west to east (pair a) and south to north
+ * (pair b).  The definition is tube.reference_tube (NumPy); csrc/tube_rows.h
+ * restates it.
+ *
+ * A point is valid iff lon and lat are finite, |lat| < pi/2 (the double
+ * nearest pi/2) and the column need, where named, is finite.  The stencil is
+ * fixed at row 0: the pair (p, q) of direction a is (W, E) if both are valid
+ * there, else (j, E), else (W, j), else none; direction b likewise.  A ray
+ * invalid at row 0, without a pair in either direction, with a channel outside
+ * [0, nchan) or with jac_0 == 0 has no tube.  At row i, one rounding per
+ * operation, no FMA:
+ *   dla = wrap(lon_q - lon_p), dpa = lat_q - lat_p       (dlb, dpb: pair b)
+ *   jac = dla * dpb - dlb * dpa;  A = jac * cos(lat_j);  D = A / A_0
+ * with wrap(d) = ((d + pi) % 2 pi) % 2 pi - pi (Python's %).  Row i is open iff
+ * j and its stencil rays are valid there, max(|dla|, |dpa|, |dlb|, |dpb|) <=
+ * max_sep and every earlier row was open; the first row that is not closes the
+ * tube for good.  An open row i >= 1 whose (jac < 0) differs from the previous
+ * row's is a caustic.  Every open row in the map adds cnt += 1, slog +=
+ * log|D| in ray j's box (binned as rwrt_ray_density bins it), a caustic
+ * ncaus += 1; an open row with jac == 0 adds 1 to dropped instead. */
+typedef struct {
+  int32_t nx, ny, nchan;
+  int32_t need;             /* row column, -1 (none) or 2..6: must be finite */
+  double lat0, inv_dlat;    /* rad; ny / (lat1 - lat0) */
+  double inv_dlon;          /* nx / (2 pi) */
+  double max_sep;           /* rad, positive; +inf: no limit */
+} rwrt_tube_map;            /* 48 bytes */
+
+#define RWRT_TUBE_NI 5      /* rows of d_state_i */
+#define RWRT_TUBE_NF 13     /* rows of d_state_f */
+
+/* Walks the tubes of all nray rays over rows it_begin <= i < it_end: ray j is
+ * column j of every per-ray array, and every ray of the run is in the launch
+ * (a ray reads its neighbours' rows).  ACCUMULATES into d_cnt, d_ncaus (int64)
+ * and d_slog (fp64), each [nchan][ny][nx], and d_dropped[1] (int64).  Row
+ * layouts and d_chan are those of rwrt_ray_density.
+ *  d_nbr[4][nray] (int32): the W, E, S, N neighbour of every ray, -1 for
+ *    none.  An index outside [-1, nray) is never followed: the ray counts as
+ *    closed and bit 0 of d_err[0] (int32) is set.
+ *  d_state_i[RWRT_TUBE_NI][nray] (int32): flags (bits 0-1 and 2-3: the pair of
+ *    direction a and b -- 0 none, 1 (lo, hi), 2 (j, hi), 3 (lo, j); bit 4:
+ *    open), mu, first (-1: none), nrow, close_row (-1: never).
+ *  d_state_f[RWRT_TUBE_NF][nray] (fp64): jac_prev, jac_0, cos_0, dmin, dlast
+ *    (signed), f0[4] and flast[4]: (dla cos, dpa, dlb cos, dpb) at row 0 and
+ *    at the last open row.
+ *    Both are a running state and the per-ray result at once: the calls
+ *    deliver CONSECUTIVE rows in order, once.  A call with it_begin == 0
+ *    fixes every stencil from its first row and starts the per-ray arrays
+ *    over; before one, flags 0 (no tube) makes every other call a no-op.
+ * One lane walks one ray and resolves its stencil rays' row blocks once per
+ * call; where a ray and its whole stencil are in their constant tails, the n
+ * remaining rows are the first of them plus ONE product (double)(n - 1) *
+ * log|D|.  64-bit integer adds and hardware fp64 adds, no compare-exchange
+ * loop.  Every integer rests on the sign of jac and is exact; D, f0 and flast
+ * differ from the definition only through cos, slog also through log and the
+ * arrival order.
+ * RWRT_ERR_ARG before any HIP call: a NULL map, d_nbr, d_state_i, d_state_f,
+ * d_cnt, d_slog, d_ncaus, d_dropped or d_err; nx, ny or nchan not positive;
+ * nchan*ny*nx >= 2^31; need outside {-1, 2..6}; inv_dlon or inv_dlat not
+ * finite and positive; lat0 not finite; max_sep not positive (NaN included);
+ * it_begin < 0; the row arguments as for rwrt_ray_density.  Asynchronous and
+ * ordered on `stream`; needs no rwrt_ctx.  nray == 0 is a no-op. */
+rwrt_status rwrt_ray_tube(const rwrt_tube_map* m, int64_t nray,
+                          int32_t it_begin, int32_t it_end,
+                          const double* d_rows, const int32_t* d_row_slot,
+                          const int32_t* d_tail_from, const double* d_tail_row,
+                          const int32_t* d_chan, const int32_t* d_nbr,
+                          int32_t* d_state_i, double* d_state_f,
+                          int64_t* d_cnt, double* d_slog, int64_t* d_ncaus,
+                          int64_t* d_dropped, int32_t* d_err, void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

@@ -22,7 +22,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
                "rwrt_launch_plan_bytes", "rwrt_launch_plan",
                "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival", "rwrt_ray_flux",
-               "rwrt_ray_track", "rwrt_ray_cross", "rwrt_ray_phase",
+               "rwrt_ray_track", "rwrt_ray_cross", "rwrt_ray_phase", "rwrt_ray_tube",
                "rwrt_wn_map", "rwrt_wn_fill",
                "rwrt_sh_filter",
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
@@ -145,6 +145,17 @@ class PhaseMapC(ctypes.Structure):
 
 assert ctypes.sizeof(PhaseMapC) == 56
 
+
+class TubeMapC(ctypes.Structure):
+    """``rwrt_tube_map``: the map a ``rwrt_ray_tube`` call deposits into
+    (``need``: a row column, -1 for none; ``max_sep``: radians)."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nchan", ctypes.c_int32),
+                ("need", ctypes.c_int32), ("lat0", ctypes.c_double), ("inv_dlat", ctypes.c_double),
+                ("inv_dlon", ctypes.c_double), ("max_sep", ctypes.c_double)]
+
+
+assert ctypes.sizeof(TubeMapC) == 48
+
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
 NDIAG = 23     # RWRT_NDIAG: the planes of rwrt_bs_diag
 
@@ -182,6 +193,7 @@ def load():
     T = ctypes.POINTER(TrackMapC)
     X = ctypes.POINTER(CrossMapC)
     Ph = ctypes.POINTER(PhaseMapC)
+    Tu = ctypes.POINTER(TubeMapC)
     sig = {
         "rwrt_pack_fields": [G, _P, _P, _P],
         "rwrt_mercator_point": [G, _P, _I64, _P, _P, _P, _P],
@@ -206,6 +218,7 @@ def load():
         "rwrt_ray_track": [T, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_cross": [X, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_phase": [Ph, _I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+        "rwrt_ray_tube": [Tu, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ray_summary": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _I64, R, _P, _P, _P],
         "rwrt_wn_map": [G, _P, _I32, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_wn_fill": [_I32, _I32, _I32, _I32, _P, _P, _P],

@@ -245,6 +245,10 @@ class EnsembleWR:
                 m = PhaseMap(with_channels(spec, ew.nmember), nray, device, chan)
                 m.start(ew.rlon[0], ew.rlat[0], ew.ramp[0], ew.ramp[0], k=ew.rzwn[0], l=ew.rmwn[0])
                 return m, PhaseSink(m)
+
+        A ray-tube map (tube.py) also needs the neighbours of the stack's
+        ray slots: ``lattice_neighbours(nnx, nny, nzwn, nlead=3 * nmember)``
+        (the example in tube.py's docstring).
         """
         chan, _ = self.channels(by)
         self.ray_initial()

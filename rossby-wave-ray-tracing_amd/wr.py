@@ -68,6 +68,8 @@ class WR:
         # row i of the history is the state at -i * tstep (rows index elapsed
         # steps; ug, vg are the true group velocity at the point)
         self.backward = bool(backward)
+        # the source lattice set_source_matrix remembers (ray_tube finds a ray's neighbours from it)
+        self.source_nnx = self.source_nny = self.source_dlon = self.source_cyclic_x = None
 
     def get_defualt_nlon_and_nlat(self, ncfile):
         """(nlat, nlon) from the file's lat/lon (or u's last two dims), wr.py:173-212."""
@@ -93,6 +95,7 @@ class WR:
             raise ValueError("Source list length mismatch nsource")
         self.source_lon = np.array(lon_list, dtype=self.all_dtype) * (1.0 * deg2rad)
         self.source_lat = np.array(lat_list, dtype=self.all_dtype) * (1.0 * deg2rad)
+        self.source_nnx = self.source_nny = self.source_dlon = self.source_cyclic_x = None
 
     def set_source_matrix(self, SW_lon, SW_lat, dlon, dlat, nnx, nny):
         """Regular source grid, index ``iy*nnx + ix`` (wr.py:236-258)."""
@@ -106,6 +109,8 @@ class WR:
                 idx = iy * nnx + ix
                 self.source_lon[idx] = ((SW_lon + ix * dlon) % 360.0) * deg2rad
                 self.source_lat[idx] = (SW_lat + iy * dlat) * deg2rad
+        self.source_nnx, self.source_nny, self.source_dlon = nnx, nny, dlon
+        self.source_cyclic_x = bool(nnx * dlon == 360)   # (sources all around a latitude circle)
 
     def ray_info(self):
         bar = "=" * 78
@@ -501,6 +506,47 @@ class WR:
 
         return self._ray_segments(P.reference_phase, P.PhaseMap, P.PhaseSink, spec, mode, inte_method, by, group,
                                   root_method, start=start)
+
+    def ray_tube(self, spec, by=None, nbr=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
+        """Initialise and integrate all rays like ``ray_run``, but follow the
+        tube that every ray's neighbours in the source lattice span around it
+        (tube.py) instead of delivering the history: returns the
+        ``tube.TubeMap`` -- per map box the tube points ``cnt``, the sum of
+        ``log|D|`` of the geometric spreading ``D`` and the caustics
+        (``mean_log_spreading()``, ``geometric_amplitude()``,
+        ``caustic_density()``), and per ray the Maslov index ``mu``, the row
+        of the ``first`` caustic, the open rows ``nrow``, ``close_row``,
+        ``dmin``, ``dlast`` and the tube's columns ``f0``, ``flast``
+        (``ftle(tstep)``), arrays that reshape to ``(3, nsource, nzwn)``; only
+        row 0 of ``rlon .. rvg`` is filled.
+
+        ``spec``: a ``tube.TubeSpec``.  ``by``: as in ``ray_density``.
+        ``nbr``: the W, E, S, N neighbour of every ray slot (int ``[4, 3 *
+        nsource * nzwn]``, -1: none); None: those of the lattice
+        ``set_source_matrix`` made (``tube.lattice_neighbours``, cyclic in x
+        where ``nnx * dlon == 360``) -- sources from ``set_source_array`` have
+        no lattice and need ``nbr``.  ``backward=True`` runs work unchanged:
+        the tube then says how sharply a receptor's origin is determined.
+        ``mode='numpy'`` integrates on the GPU all the same, delivers the
+        history and applies ``tube.reference_tube`` on the host (small runs;
+        returns its dict).  A process ``group`` is refused: a ray's
+        neighbours live on other ranks."""
+        import tube as Tu
+        if group is not None:
+            raise NotImplementedError("ray_tube is not sharded: a ray's neighbours live on other ranks "
+                                      "(DESIGN.md section 25 says what it would take)")
+        _check_by(by)
+        nray = 3 * self.nsource * self.nzwn
+        if nbr is None:
+            if self.source_nnx is None:
+                raise ValueError("sources from set_source_array have no lattice: pass nbr (int [4, nray]: the W, E, "
+                                 "S, N neighbour of every ray slot, -1 for none)")
+            nbr = Tu.lattice_neighbours(self.source_nnx, self.source_nny, self.nzwn, nlead=3,
+                                        cyclic_x=self.source_cyclic_x)
+        nbr = Tu.check_neighbours(nbr, nray)
+        return self._ray_segments(lambda rows, chan, sp: Tu.reference_tube(rows, nbr, chan, sp),
+                                  lambda sp, n, device, chan: Tu.TubeMap(sp, n, nbr, device, chan),
+                                  Tu.TubeSink, spec, mode, inte_method, by, None, root_method)
 
     def ray_summary(self, regions=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but reduce every
