@@ -200,14 +200,8 @@ def load():
         "rwrt_rhs": [G, _P, _I64, _P, _P, _P],
         "rwrt_dp54_attempt": [G, _P, _I64, _P, _P, _P, _D, _D, _P, _P, _P, _P],
         "rwrt_ray_initial": [G, _P, _I64, _P, _P, _P, _I32, _P, _P, _P, _P],
-        "rwrt_rk45_init": [G, _P, _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
-        "rwrt_rk45_run": [_P, G, _P, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],
-        "rwrt_rk45_run_tails": [_P, G, _P, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
-                                _P],
         "rwrt_expand_tails": [_I64, _I32, _I32, _P, _P, _P, _P],
         "rwrt_row_slots": [_I64, _P, _P, _P, _P],
-        "rwrt_rk45_run_slots": [_P, G, _P, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
-                                _P, _P],
         "rwrt_expand_slots": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P],
         "rwrt_launch_plan_bytes": [_I64, ctypes.POINTER(_I64)],
         "rwrt_launch_plan": [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, ctypes.POINTER(_I64), _P, _I64, _P],
@@ -225,17 +219,6 @@ def load():
         "rwrt_sh_filter": [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_bs_ready": [_I32, _I32, _P, _P, _P, _D, _D, _P, _P, _I32, _P],
         "rwrt_bs_diag": [_I32, _I32, _I32, _P, _P, _P, _D, _D, ctypes.c_uint32, _P, _P, _I32, _P],
-        "rwrt_rk45_init_tv": [G, B, _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
-        "rwrt_rk45_run_tv": [_P, G, B, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],
-        "rwrt_rk45_run_tv_tails": [_P, G, B, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
-                                   _P],
-        "rwrt_rk45_run_tv_slots": [_P, G, B, _I64, Pr, _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P,
-                                   _P, _P],
-        "rwrt_rk45_init_stack": [G, ctypes.POINTER(Stack), _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
-        "rwrt_rk45_run_stack": [_P, G, ctypes.POINTER(Stack), _I64, Pr, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P,
-                                _P, _P, _P],
-        "rwrt_rk45_init_rel": [G, B, _P, _I64, _P, Pr, _P, _P, _P, _P, _P, _P],
-        "rwrt_rk45_run_rel": [_P, G, B, _P, _I64, Pr, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
         "rwrt_ctx_create": [_I32, ctypes.POINTER(_P)],
         "rwrt_ctx_destroy": [_P],
         "rwrt_ctx_set_latency_density": [_P, _I32],
@@ -248,6 +231,17 @@ def load():
         "rwrt_selftest_math": [_I32, _I64, _P, _P, _P, _P],
         "rwrt_host_fill_rows": [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P],
     }
+    # The twelve rwrt_rk45_* entries, from their pieces: what lies between grid and nray per background kind;
+    # n_heavy and the layout's own row arguments for the static and the time-varying trio, all three row
+    # arguments and no n_heavy for the stack and release entries.
+    rows = {"": [], "_tails": [_P, _P], "_slots": [_P, _P, _P]}
+    for kind, bg in {"": [_P], "_tv": [B], "_stack": [ctypes.POINTER(Stack)], "_rel": [B, _P]}.items():
+        trio = kind in ("", "_tv")
+        sig["rwrt_rk45_init" + kind] = [G] + bg + [_I64, _P, Pr] + [_P] * 6
+        for layout in (rows if trio else ["_slots"]):
+            sig["rwrt_rk45_run" + kind + (layout if trio else "")] = (
+                [_P, G] + bg + [_I64, Pr, _P, _I32, _I32, _P] + ([_I64] if trio else []) + [_P] * 4 + rows[layout] +
+                [_P, _P])
     for name, args in sig.items():
         fn = getattr(lib, name, None)
         if fn is None:     # (an older A/B build: bench.py --lib; tests/test_abi.py checks ours)

@@ -4199,12 +4199,41 @@ int persistent_blocks_on(int ncu) {
 void launch_init_back(const InitArgs<StaticBG>& a, unsigned grid, hipStream_t st);
 void launch_run_back(const RunArgs<StaticBG>& a, unsigned grid, hipStream_t st);
 
-// solver construction / ray loop launchers shared by the static and the
-// time-varying entry points
+// What a rwrt_rk45_init* / rwrt_rk45_run* entry takes besides its background, as
+// include/rwrt.h names it: each entry fills one of these once (what it does not
+// take stays zero) and hands it, with the background it built, to launch_init /
+// launch_run -- the solver construction and the ray loop of every background kind.
+struct InitCall {
+  int64_t nray;
+  const double* d_y0;
+  const rwrt_params* p;
+  double* d_state;
+  int64_t* d_count;
+  int32_t *d_nanrow, *d_live;
+  int64_t* d_summary;
+  void* stream;
+};
+struct RunCall {
+  int64_t nray;
+  const rwrt_params* p;
+  const double* d_tbound;
+  int32_t it_begin, it_end;
+  const int64_t* d_order;
+  int64_t n_heavy;
+  double* d_state;
+  int64_t* d_count;
+  int32_t* d_nanrow;
+  double* d_out;
+  const int32_t* d_row_slot;
+  int32_t* d_tail_from;
+  double* d_tail_row;
+  int32_t* d_work;
+  void* stream;
+};
+
 template <class BG>
-rwrt_status launch_init(const BG& B, int64_t nray, const double* d_y0, const rwrt_params* p,
-                        double* d_state, int64_t* d_count, int32_t* d_nanrow, int32_t* d_live,
-                        int64_t* d_summary, void* stream) {
+rwrt_status launch_init(const BG& B, const InitCall& c) {
+  const auto [nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream] = c;
   if (!p) return fail(RWRT_ERR_ARG, "params is NULL%s");
   if (nray < 0 || nray > 0x7fffffffLL) return fail(RWRT_ERR_ARG, "nray out of range%s");
   // per-ray buffers of an empty batch may be NULL (empty tensors)
@@ -4225,6 +4254,22 @@ rwrt_status launch_init(const BG& B, int64_t nray, const double* d_y0, const rwr
   return check_launch("rk45_init_kernel");
 }
 
+// The background kinds of the ray loop, a closed set: each one's place in the
+// context's memo of persistent grids (rwrt_ctx::blocks).
+template <class BG> struct KindOf;
+template <> struct KindOf<StaticBG> : std::integral_constant<int, 0> {};
+template <> struct KindOf<VaryingBG<float>> : std::integral_constant<int, 1> {};
+template <> struct KindOf<VaryingBG<double>> : std::integral_constant<int, 2> {};
+template <> struct KindOf<VaryingBGA32> : std::integral_constant<int, 3> {};
+template <> struct KindOf<StackBG> : std::integral_constant<int, 4> {};
+template <> struct KindOf<ReleaseBG> : std::integral_constant<int, 5> {};
+constexpr int kKinds = 6;
+// the rays-per-wave switch of a kind whose lanes the context sets (rwrt_ctx_set_tv_lanes: the fp64
+// time-varying loops), NULL for the others
+template <class BG> int* ctx_half(BG&) { return nullptr; }
+inline int* ctx_half(VaryingBG<double>& B) { return &B.half; }
+inline int* ctx_half(ReleaseBG& B) { return &B.V.half; }
+
 }  // namespace rwrt
 
 // An execution context (include/rwrt.h rwrt_ctx): everything the ray-loop
@@ -4239,8 +4284,7 @@ rwrt_status launch_init(const BG& B, int64_t nray, const double* d_y0, const rwr
 struct rwrt_ctx {
   int device = 0;
   int ncu = 256;
-  int blocks_static = 0, blocks_f32 = 0, blocks_f64 = 0, blocks_a32 = 0;   // persistent grids
-  int blocks_stack = 0, blocks_rel = 0;
+  int blocks[rwrt::kKinds] = {};   // persistent grids, by KindOf<BG>
   int last_blocks = 0, last_block_rays = 0;   // the queue grid of the last ray-loop launch (rwrt_ctx_last_grid)
   uint8_t* flags = nullptr;
   size_t cap = 0;
@@ -4292,14 +4336,11 @@ rwrt_status ctx_flags(rwrt_ctx* c, int64_t nray) {
   return RWRT_OK;
 }
 
-// The cache image of F for this call, built on `stream` (after ctx_begin:
-// the previous call of the context, which may still read the old image, is
-// finished on the device by then).  Rebuilt every call, so a caller may change
-// the packed state between calls; ~1 MB at 2.5 degrees.
-rwrt_status ctx_image(rwrt_ctx* c, const Field& F, hipStream_t stream, const char** out,
-                      const int** range = nullptr) {
-  // the values' exponent range (bg_lean) behind the image, zeroed for the kernel's maxima
-  const size_t image = cache_image_bytes((int64_t)F.W * F.H), need = image + kRangeInts * sizeof(int);
+// Room for this call's cache image(s) in the context: `image` bytes, and behind
+// them the values' exponent range (bg_lean), *range, zeroed on `stream` for the
+// kernel's maxima.  (`whose` goes into the allocation's error text.)
+rwrt_status ctx_image_room(rwrt_ctx* c, size_t image, hipStream_t stream, const char* whose, int** range) {
+  const size_t need = image + kRangeInts * sizeof(int);
   if (need > c->img_cap) {
     if (c->img) {
       if ((c->used && hipEventSynchronize(c->done) != hipSuccess) || hipFree(c->img) != hipSuccess)
@@ -4308,12 +4349,23 @@ rwrt_status ctx_image(rwrt_ctx* c, const Field& F, hipStream_t stream, const cha
       c->img_cap = 0;
     }
     if (hipMalloc(reinterpret_cast<void**>(&c->img), need) != hipSuccess)
-      return fail(RWRT_ERR_HIP, "cache image allocation failed%s");
+      return fail(RWRT_ERR_HIP, "cache image allocation%s failed", whose);
     c->img_cap = need;
   }
-  int* r = reinterpret_cast<int*>(c->img + image);
-  if (hipMemsetAsync(r, 0, kRangeInts * sizeof(int), stream) != hipSuccess)
+  *range = reinterpret_cast<int*>(c->img + image);
+  if (hipMemsetAsync(*range, 0, kRangeInts * sizeof(int), stream) != hipSuccess)
     return check_launch("hipMemsetAsync(exponent range)");
+  return RWRT_OK;
+}
+
+// The cache image of F for this call, built on `stream` (after ctx_begin:
+// the previous call of the context, which may still read the old image, is
+// finished on the device by then).  Rebuilt every call, so a caller may change
+// the packed state between calls; ~1 MB at 2.5 degrees.
+rwrt_status ctx_image(rwrt_ctx* c, const Field& F, hipStream_t stream, const char** out,
+                      const int** range = nullptr) {
+  int* r = nullptr;
+  if (rwrt_status s = ctx_image_room(c, cache_image_bytes((int64_t)F.W * F.H), stream, "", &r)) return s;
   hipLaunchKernelGGL(cache_image_kernel, dim3(grid_for((int64_t)F.W * F.H * 6, 256)), dim3(256), 0, stream,
                      F, c->img, r);
   *out = c->img;
@@ -4328,22 +4380,10 @@ rwrt_status ctx_image(rwrt_ctx* c, const Field& F, hipStream_t stream, const cha
 // have no lean tier.)
 rwrt_status ctx_stack_images(rwrt_ctx* c, const StackBG& B, hipStream_t stream, const char** out) {
   const int64_t npts = (int64_t)B.F.W * B.F.H;
-  const size_t image = (size_t)stack_image_bytes(npts);
-  const size_t need = image * (size_t)B.nmember + kRangeInts * sizeof(int);
-  if (need > c->img_cap) {
-    if (c->img) {
-      if ((c->used && hipEventSynchronize(c->done) != hipSuccess) || hipFree(c->img) != hipSuccess)
-        return check_launch("releasing the context's cache image");
-      c->img = nullptr;
-      c->img_cap = 0;
-    }
-    if (hipMalloc(reinterpret_cast<void**>(&c->img), need) != hipSuccess)
-      return fail(RWRT_ERR_HIP, "cache image allocation for the member stack failed%s");
-    c->img_cap = need;
-  }
-  int* r = reinterpret_cast<int*>(c->img + image * (size_t)B.nmember);
-  if (hipMemsetAsync(r, 0, kRangeInts * sizeof(int), stream) != hipSuccess)
-    return check_launch("hipMemsetAsync(exponent range)");
+  int* r = nullptr;
+  if (rwrt_status s = ctx_image_room(c, (size_t)stack_image_bytes(npts) * (size_t)B.nmember, stream,
+                                     " for the member stack", &r))
+    return s;
   for (int32_t m = 0; m < B.nmember; ++m) {
     Field F = B.F;
     F.P = B.F.P + (int64_t)m * B.member_stride;
@@ -4354,17 +4394,9 @@ rwrt_status ctx_stack_images(rwrt_ctx* c, const StackBG& B, hipStream_t stream, 
   return check_launch("cache_image_kernel (member stack)");
 }
 
-template <class BG> int& ctx_blocks(rwrt_ctx* c);
-template <> int& ctx_blocks<StaticBG>(rwrt_ctx* c) { return c->blocks_static; }
-template <> int& ctx_blocks<VaryingBG<float>>(rwrt_ctx* c) { return c->blocks_f32; }
-template <> int& ctx_blocks<VaryingBG<double>>(rwrt_ctx* c) { return c->blocks_f64; }
-template <> int& ctx_blocks<VaryingBGA32>(rwrt_ctx* c) { return c->blocks_a32; }
-template <> int& ctx_blocks<StackBG>(rwrt_ctx* c) { return c->blocks_stack; }
-template <> int& ctx_blocks<ReleaseBG>(rwrt_ctx* c) { return c->blocks_rel; }
-
 template <class BG>
 int ctx_persistent_blocks(rwrt_ctx* c) {
-  int& b = ctx_blocks<BG>(c);
+  int& b = c->blocks[KindOf<BG>::value];
   if (!b) b = persistent_blocks_on<BG>(c->ncu);
   return b;
 }
@@ -4397,11 +4429,10 @@ rwrt_status ctx_check(rwrt_ctx* c) {
 }
 
 template <class BG>
-rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_params* p,
-                       const double* d_tbound, int32_t it_begin, int32_t it_end,
-                       const int64_t* d_order, int64_t n_heavy, double* d_state, int64_t* d_count,
-                       int32_t* d_nanrow, double* d_out, int32_t* d_tail_from, double* d_tail_row,
-                       int32_t* d_work, void* stream, const int32_t* d_row_slot = nullptr) {
+rwrt_status launch_run(rwrt_ctx* ctx, BG B, const RunCall& c) {
+  const auto [nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count, d_nanrow, d_out, d_row_slot,
+              d_tail_from, d_tail_row, d_work, stream] = c;
+  constexpr bool kStatic = std::is_same<BG, StaticBG>::value;   // the lean tier, the backward loop, the trace
   if (rwrt_status s = ctx_check(ctx)) return s;
   if (!p) return fail(RWRT_ERR_ARG, "params is NULL%s");
   if (nray < 0 || nray > 0x7fffffffLL) return fail(RWRT_ERR_ARG, "nray out of range%s");
@@ -4422,10 +4453,10 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   // (latency mode: quad_rays on the static background, replicated waves with
   // a block cache on the time-varying ones -- rk45_run_kernel's first
   // heavy_blocks blocks either way; none for the fp32-arithmetic variant)
-  if (n_heavy > 0 && std::is_void<typename TvBlock<BG>::type>::value && !std::is_same<BG, StaticBG>::value)
+  if (n_heavy > 0 && std::is_void<typename TvBlock<BG>::type>::value && !kStatic)
     return fail(RWRT_ERR_ARG, "latency mode (n_heavy > 0) is not built for fp32-arithmetic levels%s");
   // (check_flags: only the static entries come here with the flag)
-  const bool backward = std::is_same<BG, StaticBG>::value && (p->flags & RWRT_PARAMS_BACKWARD) != 0;
+  const bool backward = kStatic && (p->flags & RWRT_PARAMS_BACKWARD) != 0;
   // the context's settings are read once, under its lock: a concurrent
   // rwrt_ctx_set_latency_density cannot change the density between sizing the
   // latency-mode grid and launching it
@@ -4447,15 +4478,10 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   // latency-mode blocks take a CU each (their LDS does not fit beside a
   // persistent block): the persistent grid shrinks by as many CUs
   if (team_blocks) blocks = std::max<int64_t>(1, blocks - team_blocks * (blocks / ctx->ncu));
-  int64_t block_rays = 256;   // rays a block runs at once
-  // (a release stack: the context's rays per wave, read here under its lock -- the entry has not looked at ctx)
-  bool rel_half = false;
-  if constexpr (std::is_same<BG, ReleaseBG>::value) {
-    rel_half = ctx->tv_lanes == 32;
-    block_rays = rel_half ? 128 : 256;
-  } else if constexpr (BG::kTimeVarying) {
-    block_rays = B.half ? 128 : 256;
-  }
+  // (the fp64 time-varying loops: the context's rays per wave, read here under its lock -- no entry looks at ctx)
+  int* const half = ctx_half(B);
+  if (half) *half = ctx->tv_lanes == 32;
+  const int64_t block_rays = half && *half ? 128 : 256;   // rays a block runs at once
   const int64_t need = (nray - n_heavy + block_rays - 1) / block_rays;
   if (blocks > need) blocks = need;
   RunArgs<BG> a{B, nray, p->rtol, p->atol, p->min_step, p->cut_off, p->nt, it_begin, it_end,
@@ -4463,7 +4489,6 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
                 n_heavy, 0, haversine_cut(p->cut_off), nullptr};
   a.row_slot = d_row_slot;
   a.handoff = handoff;
-  if constexpr (std::is_same<BG, ReleaseBG>::value) a.B.V.half = rel_half;
   // frozen rays: flagged on `stream`, filled on the context's side stream
   // while the run kernel (which skips them) integrates the rest; `stream` then
   // waits for the fill, so the call stays one stream-ordered operation.  With
@@ -4472,11 +4497,11 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   if (rwrt_status s = ctx_flags(ctx, nray)) return s;
   a.frozen = ctx->flags + kFlagHead;
   if (rwrt_status s = ctx_begin(ctx, st, [&] {
-        hipLaunchKernelGGL(frozen_flag_kernel, dim3(grid_for(nray, 256)), dim3(256), 0, st, d_state, nray,
-                           ctx->flags + kFlagHead, d_tail_from, it_begin, it_end, d_tail_row);
+        hipLaunchKernelGGL(frozen_flag_kernel, dim3(grid_for(c.nray, 256)), dim3(256), 0, st, c.d_state, c.nray,
+                           ctx->flags + kFlagHead, c.d_tail_from, c.it_begin, c.it_end, c.d_tail_row);
       }))
     return s;
-  if constexpr (std::is_same<BG, StaticBG>::value) {
+  if constexpr (kStatic) {
     if (rwrt_status s = ctx_image(ctx, B.F, st, &a.B.img, &a.B.range)) return s;
   }
   if constexpr (std::is_same<BG, StackBG>::value) {
@@ -4488,7 +4513,7 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
   // wait for a CU on its XCD until the persistent grid drains)
   a.heavy_blocks = (int32_t)team_blocks;
   a.quad_per_wave = quad_per_wave;
-  if constexpr (std::is_same<BG, StaticBG>::value) {
+  if constexpr (kStatic) {
     a.trace = ctx->trace;
     a.trace_cap = ctx->trace ? ctx->trace_cap : 0;
   }
@@ -4498,16 +4523,16 @@ rwrt_status launch_run(rwrt_ctx* ctx, const BG& B, int64_t nray, const rwrt_para
     const int64_t grid = team_blocks + (nray > n_heavy ? blocks : 0);
     if (backward) {
       // (the forward kernels' grid: same launch bounds and LDS; the diagnostic trace is the forward kernels')
-      if constexpr (std::is_same<BG, StaticBG>::value) launch_run_back(a, (unsigned)grid, st);
-    } else if (a.trace && std::is_same<BG, StaticBG>::value) {
-      if constexpr (std::is_same<BG, StaticBG>::value) {
+      if constexpr (kStatic) launch_run_back(a, (unsigned)grid, st);
+    } else if (a.trace && kStatic) {
+      if constexpr (kStatic) {
         hipLaunchKernelGGL((rk45_run_kernel<BG, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
         hipLaunchKernelGGL((rk45_run_kernel<BG, true, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
       }
     } else {
       hipLaunchKernelGGL(rk45_run_kernel<BG>, dim3((unsigned)grid), dim3(256), 0, st, a);
       // the static state's two tiers: the launch's verdict ends one of the two at its entry
-      if constexpr (std::is_same<BG, StaticBG>::value)
+      if constexpr (kStatic)
         hipLaunchKernelGGL((rk45_run_kernel<BG, false, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
     }
     if (rwrt_status s = check_launch(backward ? "rk45_run_back_kernel" : "rk45_run_kernel")) return s;
@@ -4543,6 +4568,20 @@ rwrt_status make_varying(const rwrt_grid* g, const rwrt_background* b, VaryingBG
   B.dt = b->dt;
   B.half = 0;
   return RWRT_OK;
+}
+
+// f(B) for the time-varying background of the one storage kind b->fp32 names.
+// (fp32 == 2, then fp32 != 0, then fp64: the order in which the kernels that f
+// launches are first asked for, and so emitted.)
+template <class F>
+rwrt_status with_varying(const rwrt_grid* g, const rwrt_background* b, F f) {
+  auto as = [&](auto B) {
+    const rwrt_status s = make_varying(g, b, B);
+    return s ? s : f(B);
+  };
+  if (b && b->fp32 == 2) return as(VaryingBGA32{});
+  if (b && b->fp32) return as(VaryingBG<float>{});
+  return as(VaryingBG<double>{});
 }
 
 // a member stack from the ABI description: every check that needs no HIP call
@@ -4998,8 +5037,7 @@ rwrt_status rwrt_rk45_init(const rwrt_grid* g, const double* d_packed, int64_t n
   if (rwrt_status s = check_flags("rwrt_rk45_init", p, true)) return s;
   Field F;
   if (rwrt_status s = make_field(g, d_packed, F)) return s;
-  return launch_init(StaticBG{F}, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary,
-                     stream);
+  return launch_init(StaticBG{F}, {nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream});
 }
 
 rwrt_status rwrt_rk45_run(rwrt_ctx* ctx, const rwrt_grid* g, const double* d_packed,
@@ -5021,8 +5059,8 @@ rwrt_status rwrt_rk45_run_tails(rwrt_ctx* ctx, const rwrt_grid* g, const double*
   if (rwrt_status s = check_flags("rwrt_rk45_run_tails", p, true)) return s;
   Field F;
   if (rwrt_status s = make_field(g, d_packed, F)) return s;
-  return launch_run(ctx, StaticBG{F}, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state,
-                    d_count, d_nanrow, d_out, d_tail_from, d_tail_row, d_work, stream);
+  return launch_run(ctx, StaticBG{F}, {nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count,
+                                       d_nanrow, d_out, nullptr, d_tail_from, d_tail_row, d_work, stream});
 }
 
 rwrt_status rwrt_rk45_run_slots(rwrt_ctx* ctx, const rwrt_grid* g, const double* d_packed,
@@ -5035,8 +5073,8 @@ rwrt_status rwrt_rk45_run_slots(rwrt_ctx* ctx, const rwrt_grid* g, const double*
   if (!d_row_slot) return fail(RWRT_ERR_ARG, "rwrt_rk45_run_slots needs d_row_slot%s");
   Field F;
   if (rwrt_status s = make_field(g, d_packed, F)) return s;
-  return launch_run(ctx, StaticBG{F}, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state,
-                    d_count, d_nanrow, d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
+  return launch_run(ctx, StaticBG{F}, {nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count,
+                                       d_nanrow, d_out, d_row_slot, d_tail_from, d_tail_row, d_work, stream});
 }
 
 rwrt_status rwrt_row_slots(int64_t nray, const double* d_state, int32_t* d_row_slot, int64_t* d_nslot,
@@ -5089,19 +5127,8 @@ rwrt_status rwrt_rk45_init_tv(const rwrt_grid* g, const rwrt_background* b, int6
                               int64_t* d_count, int32_t* d_nanrow, int32_t* d_live,
                               int64_t* d_summary, void* stream) {
   if (rwrt_status s = check_flags("rwrt_rk45_init_tv", p, false)) return s;
-  if (b && b->fp32 == 2) {
-    VaryingBGA32 B;
-    if (rwrt_status s = make_varying(g, b, static_cast<VaryingBG<float>&>(B))) return s;
-    return launch_init(B, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream);
-  }
-  if (b && b->fp32) {
-    VaryingBG<float> B;
-    if (rwrt_status s = make_varying(g, b, B)) return s;
-    return launch_init(B, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream);
-  }
-  VaryingBG<double> B;
-  if (rwrt_status s = make_varying(g, b, B)) return s;
-  return launch_init(B, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream);
+  const InitCall c{nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream};
+  return with_varying(g, b, [&](const auto& B) { return launch_init(B, c); });
 }
 
 rwrt_status rwrt_rk45_run_tv(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_background* b,
@@ -5114,44 +5141,15 @@ rwrt_status rwrt_rk45_run_tv(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_backg
                                 d_count, d_nanrow, d_out, nullptr, nullptr, d_work, stream);
 }
 
-static rwrt_status run_tv(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_background* b,
-                                   int64_t nray, const rwrt_params* p, const double* d_tbound,
-                                   int32_t it_begin, int32_t it_end, const int64_t* d_order, int64_t n_heavy,
-                                   double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
-                                   int32_t* d_tail_from, double* d_tail_row, int32_t* d_work, void* stream,
-                          const int32_t* d_row_slot) {
-  if (b && b->fp32 == 2) {
-    VaryingBGA32 B;
-    if (rwrt_status s = make_varying(g, b, static_cast<VaryingBG<float>&>(B))) return s;
-    return launch_run(ctx, B, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count,
-                      d_nanrow, d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
-  }
-  if (b && b->fp32) {
-    VaryingBG<float> B;
-    if (rwrt_status s = make_varying(g, b, B)) return s;
-    return launch_run(ctx, B, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count,
-                      d_nanrow, d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
-  }
-  int lanes = 64;
-  if (ctx) {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    lanes = ctx->tv_lanes;
-  }
-  VaryingBG<double> B;
-  if (rwrt_status s = make_varying(g, b, B)) return s;
-  B.half = lanes == 32;
-  return launch_run(ctx, B, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count,
-                    d_nanrow, d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
-}
-
 rwrt_status rwrt_rk45_run_tv_tails(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_background* b,
                                    int64_t nray, const rwrt_params* p, const double* d_tbound,
                                    int32_t it_begin, int32_t it_end, const int64_t* d_order, int64_t n_heavy,
                                    double* d_state, int64_t* d_count, int32_t* d_nanrow, double* d_out,
                                    int32_t* d_tail_from, double* d_tail_row, int32_t* d_work, void* stream) {
   if (rwrt_status s = check_flags("rwrt_rk45_run_tv_tails", p, false)) return s;
-  return run_tv(ctx, g, b, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count, d_nanrow,
-                d_out, d_tail_from, d_tail_row, d_work, stream, nullptr);
+  const RunCall c{nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count, d_nanrow, d_out,
+                  nullptr, d_tail_from, d_tail_row, d_work, stream};
+  return with_varying(g, b, [&](const auto& B) { return launch_run(ctx, B, c); });
 }
 
 rwrt_status rwrt_rk45_run_tv_slots(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_background* b,
@@ -5162,8 +5160,9 @@ rwrt_status rwrt_rk45_run_tv_slots(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt
                                    int32_t* d_work, void* stream) {
   if (rwrt_status s = check_flags("rwrt_rk45_run_tv_slots", p, false)) return s;
   if (!d_row_slot) return fail(RWRT_ERR_ARG, "rwrt_rk45_run_tv_slots needs d_row_slot%s");
-  return run_tv(ctx, g, b, nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count, d_nanrow,
-                d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
+  const RunCall c{nray, p, d_tbound, it_begin, it_end, d_order, n_heavy, d_state, d_count, d_nanrow, d_out,
+                  d_row_slot, d_tail_from, d_tail_row, d_work, stream};
+  return with_varying(g, b, [&](const auto& B) { return launch_run(ctx, B, c); });
 }
 
 rwrt_status rwrt_rk45_init_stack(const rwrt_grid* g, const rwrt_stack* stack, int64_t nray,
@@ -5173,7 +5172,7 @@ rwrt_status rwrt_rk45_init_stack(const rwrt_grid* g, const rwrt_stack* stack, in
   if (rwrt_status s = check_flags("rwrt_rk45_init_stack", p, false)) return s;
   StackBG B;
   if (rwrt_status s = make_stack(g, stack, nray, B)) return s;
-  return launch_init(B, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream);
+  return launch_init(B, {nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream});
 }
 
 rwrt_status rwrt_rk45_run_stack(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_stack* stack,
@@ -5185,8 +5184,8 @@ rwrt_status rwrt_rk45_run_stack(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_st
   if (rwrt_status s = check_flags("rwrt_rk45_run_stack", p, false)) return s;
   StackBG B;
   if (rwrt_status s = make_stack(g, stack, nray, B)) return s;
-  return launch_run(ctx, B, nray, p, d_tbound, it_begin, it_end, d_order, 0, d_state, d_count, d_nanrow,
-                    d_out, d_tail_from, d_tail_row, d_work, stream, d_row_slot);
+  return launch_run(ctx, B, {nray, p, d_tbound, it_begin, it_end, d_order, 0, d_state, d_count, d_nanrow, d_out,
+                             d_row_slot, d_tail_from, d_tail_row, d_work, stream});
 }
 
 rwrt_status rwrt_rhs_tv(const rwrt_grid* g, const rwrt_background* b, int64_t n,
@@ -5194,23 +5193,11 @@ rwrt_status rwrt_rhs_tv(const rwrt_grid* g, const rwrt_background* b, int64_t n,
   if (n < 0 || !d_t || !d_y || !d_dydt) return fail(RWRT_ERR_ARG, "bad rwrt_rhs_tv arguments%s");
   if (n == 0) return RWRT_OK;
   const dim3 grid(grid_for(n, 256)), block(256);
-  if (b && b->fp32 == 2) {
-    VaryingBGA32 B;
-    if (rwrt_status s = make_varying(g, b, static_cast<VaryingBG<float>&>(B))) return s;
-    hipLaunchKernelGGL(rhs_bg_kernel<VaryingBGA32>, grid, block, 0, (hipStream_t)stream, B, n,
+  return with_varying(g, b, [&](const auto& B) {
+    hipLaunchKernelGGL(rhs_bg_kernel<std::decay_t<decltype(B)>>, grid, block, 0, (hipStream_t)stream, B, n,
                        d_t, d_y, d_dydt);
-  } else if (b && b->fp32) {
-    VaryingBG<float> B;
-    if (rwrt_status s = make_varying(g, b, B)) return s;
-    hipLaunchKernelGGL(rhs_bg_kernel<VaryingBG<float>>, grid, block, 0, (hipStream_t)stream, B, n,
-                       d_t, d_y, d_dydt);
-  } else {
-    VaryingBG<double> B;
-    if (rwrt_status s = make_varying(g, b, B)) return s;
-    hipLaunchKernelGGL(rhs_bg_kernel<VaryingBG<double>>, grid, block, 0, (hipStream_t)stream, B, n,
-                       d_t, d_y, d_dydt);
-  }
-  return check_launch("rhs_bg_kernel");
+    return check_launch("rhs_bg_kernel");
+  });
 }
 
 rwrt_status rwrt_bs_ready(int32_t nlon, int32_t nlat, const float* d_u, const float* d_v,
@@ -5400,7 +5387,7 @@ rwrt_status rwrt_rk45_init_rel(const rwrt_grid* g, const rwrt_background* b, con
   if (rwrt_status s = check_flags("rwrt_rk45_init_rel", p, false)) return s;
   ReleaseBG B;
   if (rwrt_status s = make_release("rwrt_rk45_init_rel", g, b, d_t0, nray, B)) return s;
-  return launch_init(B, nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream);
+  return launch_init(B, {nray, d_y0, p, d_state, d_count, d_nanrow, d_live, d_summary, stream});
 }
 
 rwrt_status rwrt_rk45_run_rel(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_background* b, const double* d_t0,
@@ -5411,8 +5398,8 @@ rwrt_status rwrt_rk45_run_rel(rwrt_ctx* ctx, const rwrt_grid* g, const rwrt_back
   if (rwrt_status s = check_flags("rwrt_rk45_run_rel", p, false)) return s;
   ReleaseBG B;
   if (rwrt_status s = make_release("rwrt_rk45_run_rel", g, b, d_t0, nray, B)) return s;
-  return launch_run(ctx, B, nray, p, d_tbound, it_begin, it_end, d_order, 0, d_state, d_count, d_nanrow, d_out,
-                    d_tail_from, d_tail_row, d_work, stream, d_row_slot);
+  return launch_run(ctx, B, {nray, p, d_tbound, it_begin, it_end, d_order, 0, d_state, d_count, d_nanrow, d_out,
+                             d_row_slot, d_tail_from, d_tail_row, d_work, stream});
 }
 
 }  // extern "C"

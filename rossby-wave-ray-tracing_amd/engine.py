@@ -5,6 +5,7 @@ drive.  It owns the packed field stack on the GPU and wraps every C-ABI call
 of ``include/rwrt.h``; ``integrate`` is the whole ray loop of the reference's
 ``WR.core_ray_run_rk45`` (wr.py:767-887), streamed in time chunks.
 """
+import collections
 import os
 
 import numpy as np
@@ -507,6 +508,12 @@ class RayEngine:
         return H.Stack(H.dptr(pk, F64, "packed members"), self.nmember, 0, pk.stride(0),
                        H.dptr(st["member"], torch.int32, "member"))
 
+    def _kind(self, st):
+        """The background kind (``KINDS``) of this engine's call on the rays of
+        ``st``: a time-varying engine serves plain and release runs, told apart
+        by ``"t0" in st``."""
+        return KINDS["stack" if self.nmember else "static" if self.bg is None else "release" if "t0" in st else "tv"]
+
     def init(self, y0, p, member=None, release=None):
         """Solver construction on the GPU; returns the per-ray state tensors
         (a member-stack engine: with each ray's ``member``, which ``take`` carries;
@@ -530,25 +537,14 @@ class RayEngine:
             live=torch.empty(nray, dtype=torch.int32, device=self.device),
             summary=torch.zeros(2, dtype=torch.int64, device=self.device),
             nray=nray)
-        lib = H.load()
         if self.nmember:
             st["member"] = member
-            stack = self.stack_of(st)
-            fn, bg = lib.rwrt_rk45_init_stack, ctypes_ref(stack)
-        elif self.bg is None:
-            fn, bg = lib.rwrt_rk45_init, H.dptr(self.packed)
-        elif t0 is not None:
+        if t0 is not None:
             st["t0"] = t0
-            H.check(lib.rwrt_rk45_init_rel(self.grid, ctypes_ref(self.bg), H.dptr(t0, F64, "t0"), nray, H.dptr(y0),
-                                           ctypes_ref(p), H.dptr(st["state"]), H.dptr(st["count"]),
-                                           H.dptr(st["nanrow"]), H.dptr(st["live"]), H.dptr(st["summary"]),
-                                           self._stream()))
-            return st
-        else:
-            fn, bg = lib.rwrt_rk45_init_tv, ctypes_ref(self.bg)
-        H.check(fn(self.grid, bg, nray, H.dptr(y0), ctypes_ref(p), H.dptr(st["state"]),
-                   H.dptr(st["count"]), H.dptr(st["nanrow"]), H.dptr(st["live"]),
-                   H.dptr(st["summary"]), self._stream()))
+        kind = self._kind(st)
+        H.check(getattr(H.load(), kind.init)(
+            self.grid, *kind.between(self, st), nray, H.dptr(y0), ctypes_ref(p), H.dptr(st["state"]),
+            H.dptr(st["count"]), H.dptr(st["nanrow"]), H.dptr(st["live"]), H.dptr(st["summary"]), self._stream()))
         return st
 
     @staticmethod
@@ -720,42 +716,22 @@ class RayEngine:
         ctx.set_handoff(self.handoff)
         if slots is not None and tails is None:
             raise ValueError("row slots need tails")
-        if self.nmember:
-            # one entry for the three row layouts; no latency mode
-            if n_heavy:
-                raise ValueError("member stacks have no latency mode (n_heavy must be 0)")
-            stack = self.stack_of(st)
-            H.check(lib.rwrt_rk45_run_stack(
-                ctx.handle, self.grid, ctypes_ref(stack), st["nray"], ctypes_ref(p), H.dptr(tbound, F64),
-                int(it_begin), int(it_end), H.dptr(order, torch.int64), H.dptr(st["state"]), H.dptr(st["count"]),
-                H.dptr(st["nanrow"]), H.dptr(out, F64), None if slots is None else H.dptr(slots.slot, torch.int32),
-                None if tails is None else H.dptr(tails.frm, torch.int32),
-                None if tails is None else H.dptr(tails.row, F64), H.dptr(self.work), self._stream()))
-            return
-        if "t0" in st:
-            # a release stack: one entry for the three row layouts; no latency mode
-            H.check(lib.rwrt_rk45_run_rel(
-                ctx.handle, self.grid, ctypes_ref(self.bg), H.dptr(st["t0"], F64, "t0"), st["nray"], ctypes_ref(p),
-                H.dptr(tbound, F64), int(it_begin), int(it_end), H.dptr(order, torch.int64), H.dptr(st["state"]),
-                H.dptr(st["count"]), H.dptr(st["nanrow"]), H.dptr(out, F64),
-                None if slots is None else H.dptr(slots.slot, torch.int32),
-                None if tails is None else H.dptr(tails.frm, torch.int32),
-                None if tails is None else H.dptr(tails.row, F64), H.dptr(self.work), self._stream()))
-            return
-        if self.bg is None:
-            fn, bg = (lib.rwrt_rk45_run if tails is None else lib.rwrt_rk45_run_tails if slots is None
-                      else lib.rwrt_rk45_run_slots), H.dptr(self.packed)
-        else:
-            fn, bg = (lib.rwrt_rk45_run_tv if tails is None else lib.rwrt_rk45_run_tv_tails if slots is None
-                      else lib.rwrt_rk45_run_tv_slots), ctypes_ref(self.bg)
-        args = [ctx.handle, self.grid, bg, st["nray"], ctypes_ref(p), H.dptr(tbound, F64),
-                int(it_begin), int(it_end), H.dptr(order, torch.int64), int(n_heavy),
-                H.dptr(st["state"]), H.dptr(st["count"]), H.dptr(st["nanrow"]), H.dptr(out, F64)]
-        if slots is not None:
-            args += [H.dptr(slots.slot, torch.int32)]
-        if tails is not None:
-            args += [H.dptr(tails.frm, torch.int32), H.dptr(tails.row, F64)]
-        H.check(fn(*args, H.dptr(self.work), self._stream()))
+        kind = self._kind(st)
+        if kind is KINDS["stack"] and n_heavy:
+            raise ValueError("member stacks have no latency mode (n_heavy must be 0)")
+        # the trio's entries take the row arguments of their layout, the one entry of the other kinds all three
+        rows = []
+        if slots is not None or not kind.trio:
+            rows += [H.dptr(None if slots is None else slots.slot, torch.int32)]
+        if tails is not None or not kind.trio:
+            rows += [H.dptr(None if tails is None else tails.frm, torch.int32),
+                     H.dptr(None if tails is None else tails.row, F64)]
+        fn = kind.run[(tails is not None) + (slots is not None)] if kind.trio else kind.run
+        H.check(getattr(lib, fn)(
+            ctx.handle, self.grid, *kind.between(self, st), st["nray"], ctypes_ref(p), H.dptr(tbound, F64),
+            int(it_begin), int(it_end), H.dptr(order, torch.int64), *([int(n_heavy)] if kind.trio else []),
+            H.dptr(st["state"]), H.dptr(st["count"]), H.dptr(st["nanrow"]), H.dptr(out, F64), *rows,
+            H.dptr(self.work), self._stream()))
 
     def tails(self, nray):
         """A ``Tails`` for ``nray`` rays, or None when the engine writes dense rows."""
@@ -1221,6 +1197,21 @@ def _row_buffers(out, nray, rows_max, device):
 def ctypes_ref(p):
     import ctypes
     return ctypes.byref(p)
+
+
+# The background kinds of the DP5(4) ray loop (RayEngine._kind): the init entry; the run entry, per row layout
+# (dense, tails, slots) for the trio of kinds that take n_heavy and their layout's row arguments, one for the kinds
+# that take all three row arguments (NULL where unused) and no n_heavy; the arguments between grid and nray.
+Kind = collections.namedtuple("Kind", "init run trio between")
+KINDS = {
+    "static": Kind("rwrt_rk45_init", ("rwrt_rk45_run", "rwrt_rk45_run_tails", "rwrt_rk45_run_slots"), True,
+                   lambda e, st: [H.dptr(e.packed)]),
+    "tv": Kind("rwrt_rk45_init_tv", ("rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails", "rwrt_rk45_run_tv_slots"), True,
+               lambda e, st: [ctypes_ref(e.bg)]),
+    "stack": Kind("rwrt_rk45_init_stack", "rwrt_rk45_run_stack", False, lambda e, st: [ctypes_ref(e.stack_of(st))]),
+    "release": Kind("rwrt_rk45_init_rel", "rwrt_rk45_run_rel", False,
+                    lambda e, st: [ctypes_ref(e.bg), H.dptr(st["t0"], F64, "t0")]),
+}
 
 
 def kat_rk45(kind, y0, t_eval, rtol, atol, min_step, device="cuda"):

@@ -12,11 +12,9 @@ import pytest
 
 import _hip as H
 import rwrt_oracle as O
+from support.abi import A, ENTRIES, N, params
 from support.backward import KINDS, TSTEP, background, cfg, oracle_backward, row0
 from support.bits import bitwise
-
-A = 4096          # an aligned, non-NULL "device pointer": never dereferenced by a refused call
-N = 16
 
 
 def _live(kind):
@@ -108,25 +106,9 @@ def _calls(lib, flags):
     """Every entry that takes ``rwrt_params``, with valid-looking arguments and ``flags``."""
     g, p = _grid(), _params(flags)
     gr, pr = ctypes.byref(g), ctypes.byref(p)
-    bgd = H.Background(A, 3, 0, 0.0, 21600.0)
-    stk = H.Stack(A, 3, 0, 145 * 73 * 12, A)
-    br, sr = ctypes.byref(bgd), ctypes.byref(stk)
-    run = (A, gr, A, N, pr, A, 1, 5, None, 0, A, A, A, A)
-    run_tv = (A, gr, br, N, pr, A, 1, 5, None, 0, A, A, A, A)
-    return {
-        "rwrt_rk45_init": lambda: lib.rwrt_rk45_init(gr, A, N, A, pr, A, A, A, A, A, None),
-        "rwrt_rk45_run": lambda: lib.rwrt_rk45_run(*run, A, None),
-        "rwrt_rk45_run_tails": lambda: lib.rwrt_rk45_run_tails(*run, A, A, A, None),
-        "rwrt_rk45_run_slots": lambda: lib.rwrt_rk45_run_slots(*run, A, A, A, A, None),
-        "rwrt_rk4_run": lambda: lib.rwrt_rk4_run(A, gr, A, N, pr, 1, 5, None, A, A, A, A, A, None),
-        "rwrt_rk45_init_tv": lambda: lib.rwrt_rk45_init_tv(gr, br, N, A, pr, A, A, A, A, A, None),
-        "rwrt_rk45_run_tv": lambda: lib.rwrt_rk45_run_tv(*run_tv, A, None),
-        "rwrt_rk45_run_tv_tails": lambda: lib.rwrt_rk45_run_tv_tails(*run_tv, A, A, A, None),
-        "rwrt_rk45_run_tv_slots": lambda: lib.rwrt_rk45_run_tv_slots(*run_tv, A, A, A, A, None),
-        "rwrt_rk45_init_stack": lambda: lib.rwrt_rk45_init_stack(gr, sr, N, A, pr, A, A, A, A, A, None),
-        "rwrt_rk45_run_stack": lambda: lib.rwrt_rk45_run_stack(A, gr, sr, N, pr, A, 1, 5, None, A, A, A, A, None,
-                                                               None, None, A, None),
-    }
+    calls = {name: (lambda e=e: e(lib, p=params(flags=flags))) for name, e in ENTRIES.items()}
+    calls["rwrt_rk4_run"] = lambda: lib.rwrt_rk4_run(A, gr, A, N, pr, 1, 5, None, A, A, A, A, A, None)
+    return calls
 
 
 HONOUR = ("rwrt_rk45_init", "rwrt_rk45_run", "rwrt_rk45_run_tails", "rwrt_rk45_run_slots")

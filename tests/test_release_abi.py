@@ -5,44 +5,9 @@ and an empty batch is a no-op."""
 import ctypes
 
 import _hip as H
+from support.abi import A, ENTRIES, NROW, background, grid, params
 
-A = 4096          # an aligned, non-NULL "device pointer": never dereferenced by a refused call
-N = 16
-NCOL, NROW = 145, 73
-
-
-def grid(ncol=NCOL, nrow=NROW):
-    return H.Grid(ncol, nrow, 0.0, 0.04363323, -1.5707964, 0.04363323)
-
-
-def params(nt=181, flags=0):
-    return H.Params(1e-6, 1e-6, 7.2, 0.2, nt, flags, 7200.0)
-
-
-def background(levels=A, nlev=5, fp32=0, t0=0.0, dt=21600.0):
-    return H.Background(levels, nlev, fp32, t0, dt)
-
-
-def _ref(x):
-    return ctypes.byref(x) if x is not None else None
-
-
-def run(lib, ctx=A, g=True, b=True, t0=A, nray=N, p=True, tbound=A, i0=1, i1=5, order=None, state=A, count=A,
-        nanrow=A, out=A, slot=None, tail_from=None, tail_row=None, work=A):
-    g = grid() if g is True else g
-    b = background() if b is True else b
-    p = params() if p is True else p
-    return lib.rwrt_rk45_run_rel(ctx, _ref(g), _ref(b), t0, nray, _ref(p), tbound, i0, i1, order, state, count,
-                                 nanrow, out, slot, tail_from, tail_row, work, None)
-
-
-def init(lib, g=True, b=True, t0=A, nray=N, y0=A, p=True, state=A, count=A, nanrow=A, live=A, summary=A):
-    g = grid() if g is True else g
-    b = background() if b is True else b
-    p = params() if p is True else p
-    return lib.rwrt_rk45_init_rel(_ref(g), _ref(b), t0, nray, y0, _ref(p), state, count, nanrow, live, summary, None)
-
-
+run, init = ENTRIES["rwrt_rk45_run_rel"], ENTRIES["rwrt_rk45_init_rel"]   # (keyword callers, valid-looking defaults)
 NAMES = {run: b"rwrt_rk45_run_rel", init: b"rwrt_rk45_init_rel"}
 
 

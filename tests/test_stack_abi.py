@@ -4,44 +4,9 @@ RWRT_ERR_ARG with a message; an empty batch is a no-op."""
 import ctypes
 
 import _hip as H
+from support.abi import A, ENTRIES, NPTS, NROW, grid, stack
 
-A = 4096          # an aligned, non-NULL "device pointer": never dereferenced by a refused call
-N = 16
-NCOL, NROW = 145, 73
-NPTS = NCOL * NROW
-
-
-def grid(ncol=NCOL, nrow=NROW):
-    return H.Grid(ncol, nrow, 0.0, 0.04363323, -1.5707964, 0.04363323)
-
-
-def params(nt=181):
-    return H.Params(1e-6, 1e-6, 7.2, 0.2, nt, 0, 7200.0)
-
-
-def stack(packed=A, nmember=3, stride=NPTS * 12, member=A):
-    return H.Stack(packed, nmember, 0, stride, member)
-
-
-def run(lib, ctx=A, g=True, s=True, nray=N, p=True, tbound=A, i0=1, i1=5, order=None, state=A, count=A,
-        nanrow=A, out=A, slot=None, tail_from=None, tail_row=None, work=A):
-    g = grid() if g is True else g
-    s = stack() if s is True else s
-    p = params() if p is True else p
-    return lib.rwrt_rk45_run_stack(ctx, ctypes.byref(g) if g is not None else None,
-                                   ctypes.byref(s) if s is not None else None, nray,
-                                   ctypes.byref(p) if p is not None else None, tbound, i0, i1, order, state,
-                                   count, nanrow, out, slot, tail_from, tail_row, work, None)
-
-
-def init(lib, g=True, s=True, nray=N, y0=A, p=True, state=A, count=A, nanrow=A, live=A, summary=A):
-    g = grid() if g is True else g
-    s = stack() if s is True else s
-    p = params() if p is True else p
-    return lib.rwrt_rk45_init_stack(ctypes.byref(g) if g is not None else None,
-                                    ctypes.byref(s) if s is not None else None, nray, y0,
-                                    ctypes.byref(p) if p is not None else None, state, count, nanrow, live,
-                                    summary, None)
+run, init = ENTRIES["rwrt_rk45_run_stack"], ENTRIES["rwrt_rk45_init_stack"]   # (keyword callers, valid-looking defaults)
 
 
 def refused(lib, st, word):
