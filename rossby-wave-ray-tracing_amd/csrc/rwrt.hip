@@ -26,10 +26,21 @@
 #include "rwrt.h"
 #include "nproots.h"
 
-// RARE(c): the condition of a rarely taken branch.  The static analysis build
-// (-DRWRT_ANALYZE_HOT, tools/hot_count.py; never loaded) compiles those branches
-// away so that the run kernel's loop is its common path, straight-line, and
-// its static instruction count is the dynamic count of an attempt.
+// RARE(c): the condition of a rarely taken branch.  The product build gives
+// the branch its weight (taken once in 10^4), so that block placement lays the
+// branch's body out behind the loop it belongs to and not inside it: the ray
+// loop's common path with its refills is then contiguous and smaller than the
+// instruction cache ("Code layout"; tools/hot_layout.py
+// measures it, tests/test_hot_layout_host.py gates it).  The weight changes
+// where instructions lie, never which ones run.  (RWRT_RARE_WEIGHTS=0: no
+// weights, the layout before them -- A/B builds.)
+// The static analysis build (-DRWRT_ANALYZE_HOT, tools/hot_count.py; never
+// loaded) compiles those branches away so that the run kernel's loop is its
+// common path, straight-line, and its static instruction count is the dynamic
+// count of an attempt.
+#ifndef RWRT_RARE_WEIGHTS
+#define RWRT_RARE_WEIGHTS 1
+#endif
 #ifdef RWRT_ANALYZE_HOT
 // (the condition is still computed: its lane mask is consumed by an empty asm)
 __device__ __forceinline__ bool rwrt_rare_sink(bool c) {
@@ -37,6 +48,8 @@ __device__ __forceinline__ bool rwrt_rare_sink(bool c) {
   return false;
 }
 #define RARE(c) rwrt_rare_sink(c)
+#elif RWRT_RARE_WEIGHTS
+#define RARE(c) __builtin_expect_with_probability(!!(c), 0, 0.9999)
 #else
 #define RARE(c) (c)
 #endif
