@@ -45,8 +45,10 @@ extern "C" {
                                   (rwrt_ray_flux), the residence-time maps along ray
                                   segments (rwrt_ray_track), the gate-crossing maps
                                   (rwrt_ray_cross), the WKB phase along rays with its
-                                  wave-field maps (rwrt_ray_phase) and the ray-tube maps
-                                  (rwrt_ray_tube): no earlier signature or layout changed */
+                                  wave-field maps (rwrt_ray_phase), the ray-tube maps
+                                  (rwrt_ray_tube) and the Helmholtz decomposition with
+                                  the Rossby-wave source (rwrt_sh_helmholtz,
+                                  rwrt_sh_rws): no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -297,6 +299,62 @@ rwrt_status rwrt_sh_filter(int32_t nlon, int32_t nlat, int32_t nfield, int32_t t
                            const float* d_in, const double* d_w, const double* d_x,
                            double* d_spec, float* d_out32, double* d_out64,
                            double* d_scratch, void* stream);
+
+/* Helmholtz decomposition of a batch of winds (u, v) on the filter's grid (the
+ * grid, d_w and d_x of rwrt_sh_filter): vorticity and divergence, the
+ * streamfunction and the velocity potential, the rotational and the divergent
+ * wind and the vorticity gradient, all truncated triangularly at `trunc`.
+ * The definition is helmholtz.reference_helmholtz; the vector basis
+ * (b_lm = m p_lm / cos(lat) and d_lm = dp_lm/dlat, finite at the pole nodes) is
+ * csrc/sh_vector.h.  The planes of a call are a mask of the bits below; they
+ * are written in bit order.  vrt_x = (1 / (a cos(lat))) d vrt / d lon,
+ * vrt_y = (1 / a) d vrt / d lat, a = 6.3712e6 m. */
+#define RWRT_SHV_VRT   0x001u  /* relative vorticity                     */
+#define RWRT_SHV_DIV   0x002u  /* divergence                             */
+#define RWRT_SHV_PSI   0x004u  /* streamfunction                         */
+#define RWRT_SHV_CHI   0x008u  /* velocity potential                     */
+#define RWRT_SHV_UROT  0x010u  /* rotational wind, zonal component       */
+#define RWRT_SHV_VROT  0x020u  /*                  meridional component  */
+#define RWRT_SHV_UDIV  0x040u  /* divergent wind, zonal component        */
+#define RWRT_SHV_VDIV  0x080u  /*                 meridional component   */
+#define RWRT_SHV_VRTX  0x100u  /* vorticity gradient, zonal component    */
+#define RWRT_SHV_VRTY  0x200u  /*                     meridional component */
+#define RWRT_SHV_NPLANE 10
+/*  d_u, d_v [npair][nlat][nlon] float32, file layout, latitude ascending.
+ *  d_spec [npair][2][trunc+1][trunc+1][2]: vrt_lm, then div_lm (re, im) at
+ *    [l][m]; zero for l < m, for l = 0 and for orders above
+ *    min(trunc, nlon/2 - 1).  Always written.
+ *  d_out64 [npair][popcount(planes)][nlat][nlon]: the planes, in bit order.
+ *  d_rot32 [npair][2][nlat][nlon] or NULL: u_rot, v_rot of d_out64 rounded to
+ *    float32 (what rwrt_bs_ready reads); needs both bits in `planes`.
+ *  d_out64 NULL: with d_rot32 NULL coefficients only; with d_rot32 only for
+ *    planes == RWRT_SHV_UROT | RWRT_SHV_VROT (nothing but the float32 pair).
+ *  d_scratch: npair*(4 + popcount(planes))*(trunc+1)*nlat*2 doubles.
+ * RWRT_ERR_ARG: nlat even or < 3, nlon odd, trunc < 1 or > (nlat-1)/2, an empty
+ * mask or unknown bits, npair < 0 or npair * max(2, popcount) > 65535, d_u, d_v,
+ * d_out64, d_rot32 overlapping, a NULL buffer, or a row (nlon) or an order
+ * (trunc) too large for LDS.  npair == 0 is a no-op.  Every sum has a fixed
+ * order (no atomics): a call's output is bit-identical from call to call, and
+ * a pair's result does not depend on the batch it is in, nor a plane's on the
+ * other planes asked for.  Asynchronous and ordered on `stream`; needs no
+ * rwrt_ctx. */
+rwrt_status rwrt_sh_helmholtz(int32_t nlon, int32_t nlat, int32_t npair, int32_t trunc, uint32_t planes,
+                              const float* d_u, const float* d_v, const double* d_w, const double* d_x,
+                              double* d_spec, double* d_out64, float* d_rot32,
+                              double* d_scratch, void* stream);
+
+/* The Rossby-wave source of Sardeshmukh & Hoskins (1988), pointwise from planes
+ * of two decompositions A and B, each [nfield][nlat][nlon] fp64 (the
+ * definition is helmholtz.reference_rws):
+ *   S = -(vrt_B + f) div_A - (udiv_A vrtx_B + vdiv_A (vrty_B + beta)),
+ *   f = 2 Omega sin(lat), beta = 2 Omega cos(lat) / a; planetary == 0: f = beta = 0.
+ * d_x as in rwrt_sh_filter.  RWRT_ERR_ARG: the grid, nfield < 0 (or > 65535),
+ * planetary not 0 or 1, a NULL buffer, d_out overlapping a plane.  nfield == 0
+ * is a no-op.  One kernel, asynchronous on `stream`; needs no rwrt_ctx. */
+rwrt_status rwrt_sh_rws(int32_t nlon, int32_t nlat, int32_t nfield, int32_t planetary, const double* d_x,
+                        const double* d_div_a, const double* d_udiv_a, const double* d_vdiv_a,
+                        const double* d_vrt_b, const double* d_vrtx_b, const double* d_vrty_b,
+                        double* d_out, void* stream);
 
 /* Solver construction: RungeKutta.__init__ (rkf45.py:335-366) with
  * select_initial_step (rkf45.py:34-99) on d_y0[5][nray].

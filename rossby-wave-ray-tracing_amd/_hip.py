@@ -24,7 +24,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival", "rwrt_ray_flux",
                "rwrt_ray_track", "rwrt_ray_cross", "rwrt_ray_phase", "rwrt_ray_tube",
                "rwrt_wn_map", "rwrt_wn_fill",
-               "rwrt_sh_filter",
+               "rwrt_sh_filter", "rwrt_sh_helmholtz", "rwrt_sh_rws",
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
                "rwrt_rk45_run_tv_slots", "rwrt_rhs_tv",
                "rwrt_rk45_init_stack", "rwrt_rk45_run_stack",
@@ -158,6 +158,8 @@ assert ctypes.sizeof(TubeMapC) == 48
 
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
 NDIAG = 23     # RWRT_NDIAG: the planes of rwrt_bs_diag
+# RWRT_SHV_*: the planes of rwrt_sh_helmholtz, in bit (and output) order
+SHV_PLANES = ("vrt", "div", "psi", "chi", "u_rot", "v_rot", "u_div", "v_div", "vrt_x", "vrt_y")
 
 
 class SummaryRegions(ctypes.Structure):
@@ -250,6 +252,28 @@ def load():
         fn.restype = ctypes.c_int
     _lib = lib
     return lib
+
+
+# Entry points bound apart from load()'s table.  The argtypes set on the
+# library's attributes are pinned, all of them, by a record that is not taken
+# again (tests/test_ray_loop_entries_host.py), so an entry added after it keeps
+# its typed binding in a function object of its own: entry(name).
+LATER_SIGNATURES = {
+    "rwrt_sh_helmholtz": [_I32, _I32, _I32, _I32, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rwrt_sh_rws": [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+}
+_entries = {}
+
+
+def entry(name):
+    """The typed binding of an entry point of ``LATER_SIGNATURES`` (raises if
+    the library was not built or lacks the symbol)."""
+    if name not in _entries:
+        fn = load()[name]           # (a function object of its own, not the attribute's)
+        fn.argtypes = LATER_SIGNATURES[name]
+        fn.restype = ctypes.c_int
+        _entries[name] = fn
+    return _entries[name]
 
 
 def version():

@@ -50,15 +50,15 @@ class BS:
         return self.lat
 
     # ---------------------------------------------------------------- input
-    def loadbs_ncfile(self, ncfile, trunc=None):
+    def loadbs_ncfile(self, ncfile, trunc=None, rotational=False):
         """Read ``u, v`` (+ ``lat``/``lon`` if present) from a netCDF-3 or .npz file.
-        ``trunc``: as in ``load_arrays``."""
+        ``trunc``, ``rotational``: as in ``load_arrays``."""
         d = ncio.read(ncfile)
         lat = next((d[k] for k in ("lat", "latitude", "Lat", "Latitude") if k in d), None)
         lon = next((d[k] for k in ("lon", "longitude", "Lon", "Longitude") if k in d), None)
-        self.load_arrays(d["u"], d["v"], lat, lon, trunc=trunc)
+        self.load_arrays(d["u"], d["v"], lat, lon, trunc=trunc, rotational=rotational)
 
-    def load_arrays(self, u, v, lat=None, lon=None, trunc=None):
+    def load_arrays(self, u, v, lat=None, lon=None, trunc=None, rotational=False):
         """``loadbs_ncfile`` on in-memory arrays: ``u, v`` as ``(nlat, nlon)``, degrees.
 
         ``trunc`` (default None: nothing changes, no GPU is touched): ``u, v``
@@ -66,10 +66,31 @@ class BS:
         after reading (``shsf.SHFilter``, the reference's ``SHSF.py``) -- in
         the file's own latitude order, before the descending-latitude rule
         below.  Raises ``ValueError`` when the axes are not the filter's grid
-        (``shsf.check_grid``)."""
+        (``shsf.check_grid``).
+
+        ``rotational`` (default False; needs ``trunc``): ``u, v`` are replaced by
+        their rotational wind at truncation ``trunc`` instead, in float32
+        (``helmholtz.Helmholtz.rotational``: the dispersion relation holds for a
+        non-divergent basic state).  The decomposition always sees ascending
+        latitude: a descending file is flipped for the call and flipped back,
+        so the descending-latitude rule below sees what it saw before."""
+        if rotational and trunc is None:
+            raise ValueError("rotational=True needs trunc (the rotational wind is a truncated expansion)")
         u = np.array(u, dtype=self.all_dtype)
         v = np.array(v, dtype=self.all_dtype)
-        if trunc is not None:
+        if rotational:
+            import shsf
+            shsf.check_grid(self.nlat, self.nlon, lat)
+            if u.shape != (self.nlat, self.nlon) or v.shape != (self.nlat, self.nlon):
+                raise ValueError(f"u, v must be [{self.nlat}, {self.nlon}]")
+            import helmholtz
+            flip = lat is not None and np.asarray(lat)[0] > np.asarray(lat)[-1]
+            ur, vr = helmholtz.Helmholtz(self.nlat, self.nlon, trunc).rotational(
+                np.ascontiguousarray(u[::-1]) if flip else u, np.ascontiguousarray(v[::-1]) if flip else v)
+            ur, vr = ur.cpu().numpy(), vr.cpu().numpy()
+            u = (ur[::-1] if flip else ur).astype(self.all_dtype)
+            v = (vr[::-1] if flip else vr).astype(self.all_dtype)
+        elif trunc is not None:
             import shsf
             shsf.check_grid(self.nlat, self.nlon, lat)
             if u.shape != (self.nlat, self.nlon) or v.shape != (self.nlat, self.nlon):

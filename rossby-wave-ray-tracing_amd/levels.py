@@ -71,7 +71,7 @@ class Levels:
         if not (lat_deg[0] < lat_deg[-1]):
             raise ValueError("Levels needs an ascending latitude axis (flip u, v, lat first)")
         self.nlat, self.nlon = len(lat_deg), len(lon_deg)
-        self.lat_deg, self._filters, self._diag = lat_deg, {}, None
+        self.lat_deg, self._filters, self._diag, self._helmholtz = lat_deg, {}, None, {}
         # the axes exactly as BS.loadbs_ncfile builds them (float32 arithmetic)
         b = BS(self.nlon, self.nlat)
         b.load_arrays(np.zeros((self.nlat, self.nlon), np.float32),
@@ -94,18 +94,29 @@ class Levels:
         from engine import grid_of
         return grid_of(self.lon, self.lat, self.nlon + 1)
 
-    def set_level(self, j, u, v, trunc=None):
+    def set_level(self, j, u, v, trunc=None, rotational=False):
         """Build level ``j`` from ``u, v[nlat, nlon]`` (float32, file layout; host
         arrays or device tensors) with ``rwrt_bs_ready`` (asynchronous).
         ``trunc``: first truncate ``u, v`` at that spherical-harmonic degree
-        (``shsf.SHFilter``, one two-field batch; nothing leaves the device)."""
+        (``shsf.SHFilter``, one two-field batch; nothing leaves the device).
+        ``rotational`` (needs ``trunc``): the level is built from the rotational
+        wind ``u_rot, v_rot`` at that truncation instead
+        (``helmholtz.Helmholtz.rotational``, float32)."""
+        self._check_rotational(trunc, rotational)
         u = torch.as_tensor(u, dtype=torch.float32).to(self.device).contiguous()
         v = torch.as_tensor(v, dtype=torch.float32).to(self.device).contiguous()
         if u.shape != (self.nlat, self.nlon) or v.shape != (self.nlat, self.nlon):
             raise ValueError(f"u, v must be [{self.nlat}, {self.nlon}]")
-        if trunc is not None:
+        if rotational:
+            u, v = (t.contiguous() for t in self.helmholtz(trunc).rotational(u, v))
+        elif trunc is not None:
             u, v = self.sh_filter(trunc).filter(torch.stack([u, v]))
         self._ready(j, u, v)
+
+    @staticmethod
+    def _check_rotational(trunc, rotational):
+        if rotational and trunc is None:
+            raise ValueError("rotational=True needs trunc (the rotational wind is a truncated expansion)")
 
     def _ready(self, j, u, v):
         H.check(H.load().rwrt_bs_ready(self.nlon, self.nlat, H.dptr(u), H.dptr(v),
@@ -117,18 +128,34 @@ class Levels:
                                            H.dptr(self.scratch), self.level0_f64.data_ptr(), 0,
                                            H.stream(self.device)))
 
-    def set_levels(self, u, v, trunc=None):
+    def set_levels(self, u, v, trunc=None, rotational=False):
         """Build every level from ``u, v[nlev, nlat, nlon]``; with ``trunc`` the
-        whole batch of ``2 nlev`` fields is filtered in one call first."""
+        whole batch of ``2 nlev`` fields is filtered in one call first, with
+        ``rotational`` as well (see ``set_level``) replaced by its rotational
+        wind in one call."""
+        self._check_rotational(trunc, rotational)
         u = torch.as_tensor(u, dtype=torch.float32).to(self.device).contiguous()
         v = torch.as_tensor(v, dtype=torch.float32).to(self.device).contiguous()
         shape = (self.nlev, self.nlat, self.nlon)
         if u.shape != shape or v.shape != shape:
             raise ValueError(f"u, v must be [{self.nlev}, {self.nlat}, {self.nlon}]")
-        if trunc is not None:
+        if rotational:
+            u, v = self.helmholtz(trunc).rotational(u, v)
+        elif trunc is not None:
             u, v = self.sh_filter(trunc).filter(torch.stack([u, v]))
         for j in range(self.nlev):
-            self._ready(j, u[j], v[j])
+            self._ready(j, u[j].contiguous(), v[j].contiguous())
+
+    def helmholtz(self, trunc):
+        """The ``helmholtz.Helmholtz`` of this grid at ``trunc`` (kept).  Raises
+        ``ValueError`` when the axes are not the filter's grid."""
+        import helmholtz
+        import shsf
+        trunc = int(trunc)
+        if trunc not in self._helmholtz:
+            shsf.check_grid(self.nlat, self.nlon, self.lat_deg)
+            self._helmholtz[trunc] = helmholtz.Helmholtz(self.nlat, self.nlon, trunc, self.device)
+        return self._helmholtz[trunc]
 
     def sh_filter(self, trunc):
         """The ``shsf.SHFilter`` of this grid at ``trunc`` (kept).  Raises
