@@ -46,9 +46,10 @@ extern "C" {
                                   segments (rwrt_ray_track), the gate-crossing maps
                                   (rwrt_ray_cross), the WKB phase along rays with its
                                   wave-field maps (rwrt_ray_phase), the ray-tube maps
-                                  (rwrt_ray_tube) and the Helmholtz decomposition with
+                                  (rwrt_ray_tube), the Helmholtz decomposition with
                                   the Rossby-wave source (rwrt_sh_helmholtz,
-                                  rwrt_sh_rws): no earlier signature or layout changed */
+                                  rwrt_sh_rws) and the caustic-aware wave-field maps
+                                  (rwrt_ray_wave): no earlier signature or layout changed */
 #define RWRT_NFIELD_REF 18  /* BS.fields[..., 18]            (bs.py:349-368) */
 #define RWRT_NFIELD_PACK 12 /* 11 hot fields + 1 pad per grid point           */
 #define RWRT_NVAR 5         /* y = (lon, lat, k, l, amp)     (wr.py:768-776)  */
@@ -972,6 +973,87 @@ rwrt_status rwrt_ray_tube(const rwrt_tube_map* m, int64_t nray,
                           int32_t* d_state_i, double* d_state_f,
                           int64_t* d_cnt, double* d_slog, int64_t* d_ncaus,
                           int64_t* d_dropped, int32_t* d_err, void* stream);
+
+/* ABI 5, additive: caustic-aware wave-field maps.  The WKB wave of a ray is
+ * A |D|^(-1/2) exp(i (theta - mu pi / 2)): rwrt_ray_phase integrates theta and
+ * knows no caustic, rwrt_ray_tube finds D and the Maslov index mu and keeps
+ * only the last of each.  Here one lane walks both, so that every row deposits
+ * with the mu and the D it has there.  The definition is wave.reference_wave
+ * (NumPy), a composition of the two definitions above; csrc/wave_rows.h
+ * composes csrc/tube_rows.h and csrc/phase_rows.h in the same way.
+ *
+ * Per row i of ray j: open_i, jac_i, D_i and the running mu_i (a caustic at
+ * row i counted) are rwrt_ray_tube's, with need and max_sep; theta_i, nseg and
+ * the validity of the row are rwrt_ray_phase's, with need, wcol and omega_dt.
+ * theta runs over every phase-valid row whether the tube is open or not.  Row
+ * i deposits iff it is phase-valid, the tube is open there and the point lies
+ * in the map, binned by position alone as rwrt_ray_tube bins it.  Then, in
+ * this order, one rounding per operation, no FMA:
+ *   jac_i == 0                      dropped += 1, nothing else
+ *   |jac_i| < d_floor * |jac_0|     clipped += 1, nothing else
+ *   w = wv (the column wcol, 1.0 without one); spread: w = wv / sqrt(|D_i|)
+ *   psi = (theta_i - omega_dt * (double)i) - (double)mu_i * HALF_PI
+ *   psi or w not finite             dropped += 1, nothing else
+ *   cnt += 1, re += w cos(psi), im += w sin(psi), wabs += |w|
+ * with HALF_PI the double nearest pi / 2. */
+typedef struct {
+  int32_t nx, ny, nchan;
+  int32_t need, wcol;       /* row columns, -1 (none) or 2..6: must be finite / weighs the deposit */
+  int32_t spread;           /* 1: divide the weight by sqrt(|D|); 0: the Maslov phase alone */
+  double lat0, inv_dlat;    /* rad; ny / (lat1 - lat0) */
+  double inv_dlon;          /* nx / (2 pi) */
+  double max_sep;           /* rad, positive; +inf: no limit */
+  double omega_dt;          /* the wave's frequency times the row interval, rad per row */
+  double d_floor;           /* finite, >= 0: a deposit with |jac| below d_floor |jac_0| is clipped */
+} rwrt_wave_map;            /* 72 bytes */
+
+#define RWRT_WAVE_NI 6      /* rows of d_state_i */
+#define RWRT_WAVE_NF 9      /* rows of d_state_f */
+
+/* Walks the tube and the phase of all nray rays over rows it_begin <= i <
+ * it_end: ray j is column j of every per-ray array, and every ray of the run
+ * is in the launch (a ray reads its neighbours' rows).  ACCUMULATES into d_cnt
+ * (int64), d_re, d_im and d_wabs (fp64), each [nchan][ny][nx], and into
+ * d_dropped[1] and d_clipped[1] (int64).  Row layouts, d_chan, d_nbr and d_err
+ * are those of rwrt_ray_tube; a ray whose channel is outside [0, nchan) is not
+ * walked and its columns stay.
+ *  d_state_i[RWRT_WAVE_NI][nray] (int32): flags, mu, first, nrow, close_row as
+ *    in rwrt_ray_tube, and nseg.
+ *  d_state_f[RWRT_WAVE_NF][nray] (fp64): the carried previous row lon (NaN:
+ *    none), lat, k, a = l / cos(lat); theta; jac_prev, jac_0, cos_0 and dlast
+ *    (signed).
+ *    Both are a running state and the per-ray result at once: the calls
+ *    deliver CONSECUTIVE rows in order, once.  The caller writes theta_0 into
+ *    theta and zeroes nseg.  A call with it_begin == 0 treats its first row as
+ *    row 0: it fixes every stencil and starts the tube's per-ray arrays over,
+ *    forgets the carried row and leaves theta and nseg as given.
+ * One lane walks one ray; while its tube is open it gathers its stencil rays'
+ * rows per row, and a ray whose tube has closed goes on integrating theta
+ * without them.  Where a ray and its whole stencil are in their constant
+ * tails, the n remaining rows are the first of them plus ONE product
+ * (double)(n - 1) * term per sum when omega_dt == 0, row by row otherwise.  One
+ * 64-bit integer add and three hardware fp64 adds per deposit, no
+ * compare-exchange loop.  Every integer, dropped and clipped rest on jac alone
+ * and are exact; theta, mu, first, nrow, close_row and dlast are bit for bit
+ * what rwrt_ray_phase and rwrt_ray_tube give for the same rows; re, im and
+ * wabs depend on cos, sqrt, sincos and the arrival order in their last bits.
+ * RWRT_ERR_ARG before any HIP call: a NULL map, d_nbr, d_state_i, d_state_f,
+ * d_cnt, d_re, d_im, d_wabs, d_dropped, d_clipped or d_err; nx, ny or nchan
+ * not positive; nchan*ny*nx >= 2^31; need or wcol outside {-1, 2..6}; spread
+ * not 0 or 1; inv_dlon or inv_dlat not finite and positive; lat0 or omega_dt
+ * not finite; max_sep not positive (NaN included); d_floor negative or not
+ * finite; it_begin < 0; the row arguments as for rwrt_ray_density.
+ * Asynchronous and ordered on `stream`; needs no rwrt_ctx.  nray == 0 is a
+ * no-op. */
+rwrt_status rwrt_ray_wave(const rwrt_wave_map* m, int64_t nray,
+                          int32_t it_begin, int32_t it_end,
+                          const double* d_rows, const int32_t* d_row_slot,
+                          const int32_t* d_tail_from, const double* d_tail_row,
+                          const int32_t* d_chan, const int32_t* d_nbr,
+                          int32_t* d_state_i, double* d_state_f,
+                          int64_t* d_cnt, double* d_re, double* d_im, double* d_wabs,
+                          int64_t* d_dropped, int64_t* d_clipped, int32_t* d_err,
+                          void* stream);
 
 /* Fixed-step RK4 ray loop, the reference's default integrator:
  * WR.core_ray_run_numpy (wr.py:702-765) with rk4_step_numpy (wr.py:583-622)

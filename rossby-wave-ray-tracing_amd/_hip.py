@@ -22,7 +22,7 @@ ABI_SYMBOLS = ("rwrt_version", "rwrt_last_error", "rwrt_ctx_create", "rwrt_ctx_d
                "rwrt_expand_tails", "rwrt_row_slots", "rwrt_rk45_run_slots", "rwrt_expand_slots",
                "rwrt_launch_plan_bytes", "rwrt_launch_plan",
                "rwrt_rk4_run", "rwrt_ray_density", "rwrt_ray_summary", "rwrt_ray_arrival", "rwrt_ray_flux",
-               "rwrt_ray_track", "rwrt_ray_cross", "rwrt_ray_phase", "rwrt_ray_tube",
+               "rwrt_ray_track", "rwrt_ray_cross", "rwrt_ray_phase", "rwrt_ray_tube", "rwrt_ray_wave",
                "rwrt_wn_map", "rwrt_wn_fill",
                "rwrt_sh_filter", "rwrt_sh_helmholtz", "rwrt_sh_rws",
                "rwrt_bs_ready", "rwrt_bs_diag", "rwrt_rk45_init_tv", "rwrt_rk45_run_tv", "rwrt_rk45_run_tv_tails",
@@ -156,6 +156,19 @@ class TubeMapC(ctypes.Structure):
 
 assert ctypes.sizeof(TubeMapC) == 48
 
+
+class WaveMapC(ctypes.Structure):
+    """``rwrt_wave_map``: the map a ``rwrt_ray_wave`` call deposits into
+    (``need`` / ``wcol``: row columns, -1 for none; ``spread``: 0 or 1;
+    ``max_sep``: radians; ``omega_dt``: radians per row)."""
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nchan", ctypes.c_int32),
+                ("need", ctypes.c_int32), ("wcol", ctypes.c_int32), ("spread", ctypes.c_int32),
+                ("lat0", ctypes.c_double), ("inv_dlat", ctypes.c_double), ("inv_dlon", ctypes.c_double),
+                ("max_sep", ctypes.c_double), ("omega_dt", ctypes.c_double), ("d_floor", ctypes.c_double)]
+
+
+assert ctypes.sizeof(WaveMapC) == 72
+
 SUMMARY_MAXREG, SUMMARY_NF64, SUMMARY_NI32 = 8, 9, 4
 NDIAG = 23     # RWRT_NDIAG: the planes of rwrt_bs_diag
 # RWRT_SHV_*: the planes of rwrt_sh_helmholtz, in bit (and output) order
@@ -261,6 +274,7 @@ def load():
 LATER_SIGNATURES = {
     "rwrt_sh_helmholtz": [_I32, _I32, _I32, _I32, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "rwrt_sh_rws": [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rwrt_ray_wave": [ctypes.POINTER(WaveMapC), _I64, _I32, _I32] + [_P] * 16,
 }
 _entries = {}
 

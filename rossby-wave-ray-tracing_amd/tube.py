@@ -185,6 +185,47 @@ def reference_tube(rows, nbr, chan, spec):
     ``f0`` / ``flast`` the columns ``(dla cos, dpa, dlb cos, dpb)`` at row 0
     and at the last open row.  Doubles as the ``mode='numpy'`` product of
     small runs."""
+    nmap = spec.nchan * spec.ny * spec.nx
+    cnt, ncaus = np.zeros(nmap, np.int64), np.zeros(nmap, np.int64)
+    slog, sabs = np.zeros(nmap), np.zeros(nmap)
+    dropped = 0
+    ray = {}
+    with np.errstate(all="ignore"):
+        for r in tube_along(rows, nbr, chan, spec, ray):
+            put = r.open & (r.idx >= 0)
+            np.add.at(ncaus, r.idx[r.caustic & put], 1)
+            zero = put & (r.jac == 0.0)
+            dropped += int(zero.sum())
+            put &= ~zero
+            np.add.at(cnt, r.idx[put], 1)
+            term = np.log(np.abs(r.D)[put])
+            np.add.at(slog, r.idx[put], term)
+            np.add.at(sabs, r.idx[put], np.abs(term))
+    sh = spec.shape
+    return {"cnt": cnt.reshape(sh), "ncaus": ncaus.reshape(sh), "slog": slog.reshape(sh), "sabs": sabs.reshape(sh),
+            "dropped": dropped, **ray}
+
+
+class TubeRow:
+    """Row ``i`` of every ray's tube, as ``tube_along`` yields it: ``open``
+    (``[nray]`` bool), ``jac``, ``D`` (float64; meaningful where open),
+    ``caustic`` (bool), ``mu`` (the running Maslov index, a caustic at this
+    row counted), ``jac0`` and ``idx`` (the box of the ray's point by position
+    alone, -1 outside the map)."""
+    __slots__ = ("i", "open", "jac", "D", "caustic", "mu", "jac0", "idx")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def tube_along(rows, nbr, chan, spec, ray):
+    """The per-row quantities of ``reference_tube``, one ``TubeRow`` per row
+    while any tube is open -- what the definition deposits from, and what
+    ``wave.reference_wave`` composes with the phase.  ``ray`` (a dict) is
+    filled with the per-ray results ``mu, first, nrow, close_row, dmin, dlast,
+    f0, flast, code``, current after every row.  Call it under
+    ``np.errstate(all='ignore')``."""
     rows = np.asarray(rows, np.float64)
     if rows.ndim != 3 or rows.shape[1] < 1 or rows.shape[2] < 7:
         raise ValueError(f"rows must be [nray, nt >= 1, >= 7], got {rows.shape}")
@@ -197,57 +238,48 @@ def reference_tube(rows, nbr, chan, spec):
     lon, lat = rows[..., 0], rows[..., 1]
     p, q, code = stencil(ok[:, 0], nbr)
     open_ = ok[:, 0] & (code[0] > 0) & (code[1] > 0) & (chan >= 0) & (chan < spec.nchan)
-    nmap = spec.nchan * spec.ny * spec.nx
-    cnt, ncaus = np.zeros(nmap, np.int64), np.zeros(nmap, np.int64)
-    slog, sabs = np.zeros(nmap), np.zeros(nmap)
     mu, nrow = np.zeros(nray, np.int32), np.zeros(nray, np.int32)
     first, close_row = np.full(nray, -1, np.int32), np.full(nray, -1, np.int32)
     dmin, dlast = np.full(nray, math.nan), np.full(nray, math.nan)
     f0, flast = np.full((4, nray), math.nan), np.full((4, nray), math.nan)
-    jprev, a0 = np.zeros(nray), np.ones(nray)
-    dropped = 0
-    with np.errstate(all="ignore"):
-        for i in range(nt):
-            if not open_.any():
-                break
-            dla, dpa = wrap(lon[q[0], i] - lon[p[0], i]), lat[q[0], i] - lat[p[0], i]
-            dlb, dpb = wrap(lon[q[1], i] - lon[p[1], i]), lat[q[1], i] - lat[p[1], i]
-            sep = np.maximum(np.maximum(np.abs(dla), np.abs(dpa)), np.maximum(np.abs(dlb), np.abs(dpb)))
-            o = open_ & ok[:, i] & ok[p[0], i] & ok[q[0], i] & ok[p[1], i] & ok[q[1], i] & (sep <= float(spec.max_sep))
-            close_row[open_ & ~o] = i
-            jac = dla * dpb - dlb * dpa
-            c = np.cos(lat[:, i])
-            if i == 0:
-                o &= jac != 0.0                       # (no tube: close_row stays -1)
-                a0 = np.where(o, jac * c, 1.0)
-            D = (jac * c) / a0
-            caus = o & ((jac < 0.0) != (jprev < 0.0)) if i else np.zeros(nray, bool)
-            mu[caus] += 1
-            first[caus & (first < 0)] = i
-            jprev = np.where(o, jac, jprev)
-            nrow[o] += 1
-            aD = np.abs(D)
-            dmin = np.where(o & ~(dmin <= aD), aD, dmin)
-            dlast = np.where(o, D, dlast)
-            cols = np.stack([dla * c, dpa, dlb * c, dpb])
-            flast = np.where(o[None, :], cols, flast)
-            if i == 0:
-                f0 = flast.copy()
-            idx = bin_index(lon[:, i], lat[:, i], None, chan, spec)
-            put = o & (idx >= 0)
-            np.add.at(ncaus, idx[caus & put], 1)
-            zero = put & (jac == 0.0)
-            dropped += int(zero.sum())
-            put &= ~zero
-            np.add.at(cnt, idx[put], 1)
-            term = np.log(aD[put])
-            np.add.at(slog, idx[put], term)
-            np.add.at(sabs, idx[put], np.abs(term))
-            open_ = o
-    sh = spec.shape
-    return {"cnt": cnt.reshape(sh), "ncaus": ncaus.reshape(sh), "slog": slog.reshape(sh), "sabs": sabs.reshape(sh),
-            "dropped": dropped, "mu": mu, "first": first, "nrow": nrow, "close_row": close_row, "dmin": dmin,
-            "dlast": dlast, "f0": f0, "flast": flast, "code": code.astype(np.int32)}
+    jprev, a0, jac0 = np.zeros(nray), np.ones(nray), np.full(nray, math.nan)
+
+    def results():
+        ray.update(mu=mu, first=first, nrow=nrow, close_row=close_row, dmin=dmin, dlast=dlast, f0=f0, flast=flast,
+                   code=code.astype(np.int32))
+
+    results()
+    for i in range(nt):
+        if not open_.any():
+            break
+        dla, dpa = wrap(lon[q[0], i] - lon[p[0], i]), lat[q[0], i] - lat[p[0], i]
+        dlb, dpb = wrap(lon[q[1], i] - lon[p[1], i]), lat[q[1], i] - lat[p[1], i]
+        sep = np.maximum(np.maximum(np.abs(dla), np.abs(dpa)), np.maximum(np.abs(dlb), np.abs(dpb)))
+        o = open_ & ok[:, i] & ok[p[0], i] & ok[q[0], i] & ok[p[1], i] & ok[q[1], i] & (sep <= float(spec.max_sep))
+        close_row[open_ & ~o] = i
+        jac = dla * dpb - dlb * dpa
+        c = np.cos(lat[:, i])
+        if i == 0:
+            o &= jac != 0.0                       # (no tube: close_row stays -1)
+            a0 = np.where(o, jac * c, 1.0)
+            jac0 = np.where(o, jac, math.nan)
+        D = (jac * c) / a0
+        caus = o & ((jac < 0.0) != (jprev < 0.0)) if i else np.zeros(nray, bool)
+        mu[caus] += 1
+        first[caus & (first < 0)] = i
+        jprev = np.where(o, jac, jprev)
+        nrow[o] += 1
+        aD = np.abs(D)
+        dmin = np.where(o & ~(dmin <= aD), aD, dmin)
+        dlast = np.where(o, D, dlast)
+        cols = np.stack([dla * c, dpa, dlb * c, dpb])
+        flast = np.where(o[None, :], cols, flast)
+        if i == 0:
+            f0 = flast.copy()
+        results()
+        yield TubeRow(i=i, open=o, jac=jac, D=D, caustic=caus, mu=mu, jac0=jac0,
+                      idx=bin_index(lon[:, i], lat[:, i], None, chan, spec))
+        open_ = o
 
 
 def sigma_max(f0, flast, xp=np):

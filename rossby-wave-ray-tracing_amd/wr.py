@@ -548,6 +548,55 @@ class WR:
                                   lambda sp, n, device, chan: Tu.TubeMap(sp, n, nbr, device, chan),
                                   Tu.TubeSink, spec, mode, inte_method, by, None, root_method)
 
+    def ray_wave(self, spec, by=None, nbr=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
+        """Initialise and integrate all rays like ``ray_run``, but walk every
+        ray's tube and its WKB phase together and deposit every point of an
+        open tube as the wave ``w |D|^(-1/2) exp(i (theta - omega_dt row - mu
+        pi / 2))`` into its box of a lon-lat map (wave.py) instead of
+        delivering the history: the wave field of ``ray_phase`` with the
+        quarter-period each caustic takes from the phase and the amplitude the
+        spreading of the tube gives.  Returns the ``wave.WaveMap`` -- per box
+        ``cnt``, ``re``, ``im`` and ``wabs`` (``field()``, ``amplitude()``,
+        ``mean_phase()``, ``coherence()``), ``dropped`` and ``clipped``, and
+        per ray ``theta``, ``nseg``, ``mu``, ``first``, ``nrow``,
+        ``close_row`` and ``dlast``, arrays that reshape to ``(3, nsource,
+        nzwn)``; only row 0 of ``rlon .. rvg`` is filled.
+
+        ``spec``: a ``wave.WaveSpec``; ``omega_dt`` is filled in as in
+        ``ray_phase`` (``freq * tstep``, negated for ``backward=True``).
+        ``by``: as in ``ray_density``.  ``nbr``: as in ``ray_tube`` (None: the
+        lattice of ``set_source_matrix``).  ``mode='numpy'`` integrates on the
+        GPU all the same, delivers the history and applies
+        ``wave.reference_wave`` on the host (small runs; returns its dict).  A
+        process ``group`` is refused: a ray's neighbours live on other
+        ranks."""
+        from dataclasses import replace
+        import tube as Tu
+        import wave as Wv
+        if group is not None:
+            raise NotImplementedError("ray_wave is not sharded: a ray's neighbours live on other ranks "
+                                      "(DESIGN.md section 27 says what is left out)")
+        _check_by(by)
+        nray = 3 * self.nsource * self.nzwn
+        if nbr is None:
+            if self.source_nnx is None:
+                raise ValueError("sources from set_source_array have no lattice: pass nbr (int [4, nray]: the W, E, "
+                                 "S, N neighbour of every ray slot, -1 for none)")
+            nbr = Tu.lattice_neighbours(self.source_nnx, self.source_nny, self.nzwn, nlead=3,
+                                        cyclic_x=self.source_cyclic_x)
+        nbr = Tu.check_neighbours(nbr, nray)
+        if spec.omega_dt == 0.0 and float(self.freq[0]) != 0.0:
+            omega_dt = float(self.freq[0]) * float(self.tstep[0])
+            spec = replace(spec, omega_dt=-omega_dt if self.backward else omega_dt)
+
+        def start(m, rank):
+            m.start(self.rlon[0], self.rlat[0], self._column(m.spec.ncol), self._column(m.spec.wcol),
+                    k=self.rzwn[0], l=self.rmwn[0])
+
+        return self._ray_segments(lambda rows, chan, sp: Wv.reference_wave(rows, nbr, chan, sp),
+                                  lambda sp, n, device, chan: Wv.WaveMap(sp, n, nbr, device, chan),
+                                  Wv.WaveSink, spec, mode, inte_method, by, None, root_method, start=start)
+
     def ray_summary(self, regions=None, mode="hip", inte_method="rk45", group=None, root_method="numpy"):
         """Initialise and integrate all rays like ``ray_run``, but reduce every
         ray's rows to a path summary on the GPU (summary.py) instead of
